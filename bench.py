@@ -1,6 +1,6 @@
 """bench.py — SEVIR 384x384 frames/sec of the conv-AE train step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,7 +13,18 @@ synthetic SEVIR-shaped frames per GPU (BASELINE.json configs[1]; weak scaling:
 global batch 32*N).  Frames are generated on the device before the timed
 region.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps and prints the line (headline fields, config, peak memory and the
+step's HBM fraction).  Everything else it can measure runs only with --full: the per-kernel read-out pass behind
+`roofline`, `kernel_breakdown` and the timed parts of `step_roofline`, the `fp32_mfma_only` and `bf16_storage` legs and
+the CPU baseline (each still switched off one by one with its --no-* option).
+
+--dump-outputs DIR writes what the last timed step computed, right after the timed region (rank 0): recon.npy
+(the reconstruction), z.npy (the latent), loss.npy and params.npy (every parameter after that step's AdamW update,
+flattened in `net.parameters()` order), all float32; an array larger than its cap in DUMP_CAP is written as a fixed
+seeded sample, so the files stay under 64 MB.  Weights (torch.manual_seed(0)) and frames (a device generator seeded
+1234 + rank) are the same on every run with the same arguments, so two builds can be compared output for output.
+
+Extra objects in the line (--full):
   roofline      the dominant kernel of the step, chosen from THIS run: every launch of
                 every entry point is timed with an event pair on its launch stream (a
                 second pass of the same K steps right after the timed region, streams
@@ -150,6 +161,41 @@ def cpu_baseline(img_size=384, batch=1):
     return {"value": batch / dt, "unit": "frames/s", "cores": cores, "kind": "port",
             "sample": f"oracle/ae_oracle.py train step (fwd+L1+bwd+AdamW), {img_size}x{img_size}, batch {batch}, "
                       f"torch CPU fp32, {cores} threads: 1 warm-up step ({cold:.1f} s, cold) + 1 timed step ({dt:.1f} s, warm)"}
+
+
+# --dump-outputs: an array with more entries than its cap is written as a fixed seeded sample of that many (flattened,
+# in index order), so the files stay under 64 MB at any --batch / --img-size (56 MB at the caps)
+DUMP_CAP = {"recon": 1 << 23, "z": 1 << 21, "loss": 1, "params": 1 << 22}
+
+
+def dump_outputs(out_dir, recon, z, loss, params):
+    """--dump-outputs: the last timed step's reconstruction, latent, loss and updated parameters as float32 .npy files"""
+    import numpy as np
+    import torch
+
+    def sample(n, name):    # None = every entry, else the sorted seeded sample of DUMP_CAP[name] indices
+        return None if n <= DUMP_CAP[name] else np.sort(np.random.default_rng(0).choice(n, DUMP_CAP[name], replace=False))
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, t in (("recon", recon), ("z", z), ("loss", loss)):
+        a = t.detach().float().cpu().numpy()
+        idx = sample(a.size, name)
+        arrays[name] = a if idx is None else a.reshape(-1)[idx]
+    # the parameters, flattened and concatenated in net.parameters() order: gathered one tensor at a time (no
+    # device-side copy of the whole model)
+    params = [p.detach().reshape(-1) for p in params]
+    sizes = np.array([p.numel() for p in params], dtype=np.int64)
+    idx = sample(int(sizes.sum()), "params")
+    if idx is None:
+        arrays["params"] = torch.cat([p.float().cpu() for p in params]).numpy()
+    else:
+        starts = np.concatenate([[0], np.cumsum(sizes)])
+        cut = np.searchsorted(idx, starts)
+        arrays["params"] = torch.cat([p[torch.from_numpy(idx[cut[i]:cut[i + 1]] - starts[i]).to(p.device)].float().cpu()
+                                      for i, p in enumerate(params)]).numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float32))
 
 
 def kernel_source_tag():
@@ -293,7 +339,14 @@ def main():
                          "(NOT the headline configuration — the line is then labelled dtype bf16)")
     ap.add_argument("--fp32-tensors", action="store_true",
                     help="with --precision medium: keep the activation tensors fp32 in HBM (round 2's 'medium')")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: per-kernel roofline read-out, fp32-MFMA-only and "
+                         "bf16-storage legs, CPU baseline (each can still be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (recon, z, loss, updated parameters) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process only starts the ranks (it never touches the GPU)
@@ -348,10 +401,14 @@ def main():
 
     xchg = []   # (start, end) event pairs around the gradient exchange, filled during the read-out pass
 
-    def step(time_exchange=False):
+    last = {}   # the last timed step's outputs, for --dump-outputs
+
+    def step(time_exchange=False, keep=False):
         opt.zero_grad(set_to_none=True)
-        recon, _ = net(x)
+        recon, z = net(x)
         loss = Fn.l1_loss(recon, x)
+        if keep:
+            last.update(recon=recon.detach(), z=z.detach())
         loss.backward()
         if time_exchange and world > 1:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -375,15 +432,17 @@ def main():
         step()
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep=args.dump_outputs is not None and i == args.steps - 1)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, last["recon"], last["z"], loss.detach(), net.parameters())
     # Per-kernel read-out for the roofline object: the same step, K more times, with an event pair
     # around every launch on its launch stream.  Streams are serialised for this pass (weight
     # gradients back on the main stream) so a launch's duration is not inflated by a concurrent one.
     prof = {}
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         Fn.set_wgrad_overlap(False)
         step()
         fence()
@@ -394,7 +453,7 @@ def main():
         Fn.set_wgrad_overlap(not args.no_overlap)
     # the same step with every GEMM on the fp32 MFMA instruction (reported beside the headline, never as `value`)
     strict = None
-    if args.precision == "highest" and ops.split_gemm_enabled() and not args.no_fp32_leg:
+    if args.full and args.precision == "highest" and ops.split_gemm_enabled() and not args.no_fp32_leg:
         ops.set_split_gemm(False)
         step()
         fence()
@@ -408,7 +467,7 @@ def main():
     # optimiser state, batch, steps and warm-up rule — a side figure beside the headline, never `value`
     peak_mem_headline = torch.cuda.max_memory_allocated(dev) / 2 ** 30
     medium = None
-    if args.precision == "highest" and not args.no_medium_leg:
+    if args.full and args.precision == "highest" and not args.no_medium_leg:
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats(dev)
         ops.set_float32_matmul_precision("medium")
@@ -578,7 +637,7 @@ def main():
                  "calls_per_step": v[0] / args.steps, "ms_per_step": v[1] / args.steps,
                  "tflops": (v[2] / (v[1] * 1e-3) / 1e12) if v[2] else None,
                  "gbps": v[3] / (v[1] * 1e-3) / 1e9, "ideal_ms_per_step": v[4] / args.steps} for k, v in fam[:16]]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             del net, opt, dp
             torch.cuda.empty_cache()
             out["cpu_baseline"] = cpu_baseline(args.img_size, 4)

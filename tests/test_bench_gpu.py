@@ -1,5 +1,6 @@
 """GPU: bench.py's output contract on a small configuration (2 frames of 128x128): one JSON line with the headline
-fields, a `roofline` object computed from this run's own event timings, the whole-step fractions and the CPU baseline."""
+fields; with --full also a `roofline` object computed from this run's own event timings, the whole-step fractions and
+the CPU baseline; without it none of those, and --dump-outputs writes the last timed step's arrays."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract(dev):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--img-size", "128"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--img-size", "128", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-1000:]
@@ -60,7 +61,7 @@ def test_bench_two_ranks_one_card(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["WFAE_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "2", "--img-size", "128", "--no-fp32-leg"], cwd=ROOT, env=env, capture_output=True,
+                        "--batch", "2", "--img-size", "128", "--no-fp32-leg", "--full"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -70,3 +71,31 @@ def test_bench_two_ranks_one_card(dev):
     assert d["dp"]["ranks_seen"] == 2 and d["dp"]["backend"] == "gloo" and d["dp"]["grad_exchange_ms_per_step"] > 0
     assert abs(d["value"] - 2 * 2 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
     assert "cpu_baseline" not in d          # rank 0 at N = 1 only
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(dev, tmp_path):
+    """without --full the line carries the headline fields and nothing that needs a pass of its own; --dump-outputs
+    writes the last timed step's reconstruction, latent, loss and (a seeded sample of the) updated parameters"""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--img-size", "128", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "kernel_breakdown", "cpu_baseline", "fp32_mfma_only", "bf16_storage"):
+        assert k not in d, k
+    assert "ideal_ms" not in d["step_roofline"]
+    recon, z, loss, params = (np.load(out / f"{n}.npy") for n in ("recon", "z", "loss", "params"))
+    assert all(a.dtype == np.float32 for a in (recon, z, loss, params))
+    assert recon.shape == (2, 1, 128, 128) and np.isfinite(recon).all() and 0 <= recon.min() and recon.max() <= 1
+    assert z.shape[0] == 2 and np.isfinite(z).all()
+    assert float(loss.reshape(-1)[0]) == np.float32(d["final_loss"])
+    assert params.size == min(d["config"]["params"], 1 << 22) and np.isfinite(params).all()
+    assert sum(f.stat().st_size for f in out.iterdir()) < 64 << 20

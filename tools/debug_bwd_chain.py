@@ -3,7 +3,8 @@ autoencoder (dec.0 .. dec.4, the latent z, enc.3 .. enc.0) on a golden input.
 
     python tools/debug_bwd_chain.py --make [golden]     build container: oracle in fp32 AND fp64 on the CPU, writes
                                                         tests/golden/dbg_chain_<golden>.npz (norm + a strided sample of
-                                                        every checkpoint gradient, both precisions)
+                                                        every checkpoint gradient, both precisions; not committed:
+                                                        2.6 MB for g4_full384_b4, run --make before a check)
     python tools/debug_bwd_chain.py [golden]            GPU box: the product path against those samples
 """
 import os

@@ -1,7 +1,7 @@
-"""Turn the raw rocprofv3 outputs merged back under gpurun_out/ into the committed summaries in profiles/.
+"""Turn the raw rocprofv3 outputs of tools/gpu_profile.sh into the committed summaries in profiles/.
 
     python tools/make_profiles.py <tag>      (e.g. r01_v4)
-expects gpurun_out/prof (kernel stats), gpurun_out/pmc_fetch, gpurun_out/pmc_write, gpurun_out/bench.log
+expects OUT/prof (kernel stats), OUT/pmc_fetch, OUT/pmc_write, OUT/bench.log, OUT = $WFAE_OUT (default bench_out)
 """
 import collections
 import os
@@ -12,6 +12,7 @@ import shutil
 import sys
 
 tag = sys.argv[1]
+OUT = os.environ.get("WFAE_OUT", "bench_out")
 
 
 def one(pat):
@@ -20,8 +21,8 @@ def one(pat):
     return g[-1]
 
 
-shutil.copy(one("gpurun_out/prof/*/*kernel_stats.csv"), f"profiles/{tag}_bench_b32_384_kernel_stats.csv")
-shutil.copy("gpurun_out/bench.log", f"profiles/{tag}_bench_b32_384.json")
+shutil.copy(one(f"{OUT}/prof/*/*kernel_stats.csv"), f"profiles/{tag}_bench_b32_384_kernel_stats.csv")
+shutil.copy(f"{OUT}/bench.log", f"profiles/{tag}_bench_b32_384.json")
 
 
 def agg(path, cname):
@@ -33,8 +34,8 @@ def agg(path, cname):
     return d
 
 
-F = agg(one("gpurun_out/pmc_fetch/*/*counter_collection.csv"), "FETCH_SIZE")
-W = agg(one("gpurun_out/pmc_write/*/*counter_collection.csv"), "WRITE_SIZE")
+F = agg(one(f"{OUT}/pmc_fetch/*/*counter_collection.csv"), "FETCH_SIZE")
+W = agg(one(f"{OUT}/pmc_write/*/*counter_collection.csv"), "WRITE_SIZE")
 with open(f"profiles/{tag}_pmc_hbm_traffic_per_kernel.csv", "w") as fo:
     fo.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of: bench.py --steps 1 --warmup 1 (B=32, 384x384)\n")
     fo.write("# counter values are KiB; hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024: gfx950 FETCH_SIZE reports half of wide\n")
@@ -100,9 +101,9 @@ out["_step_total"] = {"bytes_2xfetch_plus_write": (2 * sum(v[1] for v in F.value
                       "bytes_raw_fetch_plus_write": (sum(v[1] for v in F.values()) + sum(v[1] for v in W.values())) * 1024 / nsteps,
                       "steps_in_run": nsteps}
 # the same for --precision medium (bf16 activation storage) when tools/gpu_profile.sh collected it
-if glob.glob("gpurun_out/pmc_fetch_medium/*/*counter_collection.csv") and glob.glob("gpurun_out/pmc_write_medium/*/*counter_collection.csv"):
-    Fm = agg(one("gpurun_out/pmc_fetch_medium/*/*counter_collection.csv"), "FETCH_SIZE")
-    Wm = agg(one("gpurun_out/pmc_write_medium/*/*counter_collection.csv"), "WRITE_SIZE")
+if glob.glob(f"{OUT}/pmc_fetch_medium/*/*counter_collection.csv") and glob.glob(f"{OUT}/pmc_write_medium/*/*counter_collection.csv"):
+    Fm = agg(one(f"{OUT}/pmc_fetch_medium/*/*counter_collection.csv"), "FETCH_SIZE")
+    Wm = agg(one(f"{OUT}/pmc_write_medium/*/*counter_collection.csv"), "WRITE_SIZE")
     out["_step_total_bf16"] = {"bytes_2xfetch_plus_write": (2 * sum(v[1] for v in Fm.values()) + sum(v[1] for v in Wm.values())) * 1024 / nsteps,
                                "bytes_raw_fetch_plus_write": (sum(v[1] for v in Fm.values()) + sum(v[1] for v in Wm.values())) * 1024 / nsteps,
                                "steps_in_run": nsteps}
@@ -113,8 +114,8 @@ if glob.glob("gpurun_out/pmc_fetch_medium/*/*counter_collection.csv") and glob.g
             n, fs = Fm[k]
             ws = Wm.get(k, [n, 0])[1]
             fo.write(f"\"{k}\",{n},{fs / n:.1f},{ws / n:.1f},{(2 * fs + ws) / n * 1024:.0f}\n")
-    shutil.copy(one("gpurun_out/prof_medium/*/*kernel_stats.csv"), f"profiles/{tag}_medium_bench_b32_384_kernel_stats.csv")
-    shutil.copy("gpurun_out/bench_medium.log", f"profiles/{tag}_medium_bench_b32_384.json")
+    shutil.copy(one(f"{OUT}/prof_medium/*/*kernel_stats.csv"), f"profiles/{tag}_medium_bench_b32_384_kernel_stats.csv")
+    shutil.copy(f"{OUT}/bench_medium.log", f"profiles/{tag}_medium_bench_b32_384.json")
 out["_kernel_source_tag"] = bench.kernel_source_tag()
 out["_source"] = f"{tag}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of bench.py --steps 1 --warmup 1"
 json.dump(out, open("profiles/pmc_traffic.json", "w"), indent=1)
