@@ -562,6 +562,23 @@ int wfae_ssim_bwd(const float* x, const float* y, const float* gout, float* dy, 
 int wfae_psnr(const float* pred, const float* target, float* out, int NB, int HW, int clamp01,
               void* ws, size_t ws_bytes, wfae_stream_t stream);
 
+/* ---- forecast-skill scores (pipeline/metrics.py:9-68: _hit_miss_fa_cn, crps, csi, hss; calc_metrics :86-133).
+ * pred (B, N, TC, H, W) — N = 1 for a deterministic (B, T, C, H, W) forecast — and target (B, TC, H, W); every
+ * (b, tc) plane is one image.  `thresholds` (n_thr <= 8 floats), `pool_types` (0 none, 1 avg, 2 max) and
+ * `pool_scales` (n_pools <= 3, F.*_pool2d(s, stride=s), remainder rows / columns dropped, 1 <= s <= min(H, W); the
+ * scale of a `none` pool is ignored) are HOST arrays.  clamp01 != 0 clamps both inputs to [0,1] first (:92-93).
+ * out (device, n_pools x (3 n_thr + 2) int64): per pool [tp, fn, fp] per threshold on the pooled ensemble mean
+ * (tn = cells - tp - fn - fp), the fp64 sum over pooled cells of the CRPS expression (:36-40, eps 1e-10; mean and
+ * Bessel std over the N pooled members, std 0 at N = 1) stored as the bits of a double, and the pooled cell count.
+ * Pooled values are formed in torch's CPU order (sequential row-major window sum, then / s^2; sequential sum over
+ * N, then / N), so the counts equal the reference's bit for bit.  ws: >= 200 bytes per partial block (<= 3 x 1024).
+ * ensemble_mean: out[o][k] = sum_n pred[o][n][k] / N in that order (pred.mean(dim=1)), clamp01 as above. */
+int wfae_skill_scores(const float* pred, const float* target, int64_t* out, int B, int N, int TC, int H, int W,
+                      const float* thresholds, int n_thr, const int* pool_types, const int* pool_scales, int n_pools,
+                      int clamp01, void* ws, size_t ws_bytes, wfae_stream_t stream);
+int wfae_ensemble_mean(const float* pred, float* out, int64_t outer, int N, int64_t inner, int clamp01,
+                       wfae_stream_t stream);
+
 /* ---- latent transformer of the `_tf` variant (pipeline/models/ae_64x8x8_tf.py:77-80,107-109):
  * nn.TransformerEncoderLayer(d_model=64, nhead=8, dim_feedforward=2048, dropout=0.1), post-norm, ReLU,
  * batch_first=False.  The Linear layers use wfae_linear_*.

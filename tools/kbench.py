@@ -2,7 +2,7 @@
 Times each libwfae.so entry point with events on the launch stream (interleaved
 rounds, median) and prints ms / TFLOP/s / GB/s per shape.
 
-    python tools/kbench.py [--only conv4,conv1,dconv,bn] [--batch 32] [--size 384] [--rounds 5]
+    python tools/kbench.py [--only conv4,conv1,dconv,bn,skill] [--batch 32] [--size 384] [--rounds 5]
 """
 import argparse
 import os
@@ -309,6 +309,27 @@ def main():
                 ms = timeit(lambda: ops.bn_act_fwd(x, st, 1), R); report(f"bn_act_fwd {ch}@{h}", ms, 0, 8 * n); acc("bn_fwd", ms, mult)
                 ms = timeit(lambda: ops.bn_act_bwd(dy, x, g, st, dg, db, None, 1, True), R); report(f"bn_act_bwd {ch}@{h}", ms, 0, 20 * n); acc("bn_bwd", ms, mult)
                 del x, dy
+    if "skill" in only:   # calc_metrics of a validation batch: the skill pass (csrc/skill.hip) next to SSIM / PSNR
+        import time
+        from weatherforecastingtoolkit_amd.pipeline import metrics as M
+        pred, tgt = torch.rand(B, 1, 1, S, S, device=dev), torch.rand(B, 1, 1, S, S, device=dev)
+        ens = torch.rand(B, 5, 1, 1, S, S, device=dev)
+        p, g = M._flat(pred), M._flat(tgt)
+        n = pred.numel()
+        for tag, x in (("B,1", pred), ("B,5 ensemble", ens)):
+            ms = timeit(lambda: ops.skill_scores(x, tgt, M.THRESHOLDS, M.POOLS, clamp01=True), R)
+            report(f"skill_scores 3 pools x 6 thr {tag} @{S}", ms, 0, 4 * (x.numel() + n))
+        ms = timeit(lambda: ops.ssim_fwd(g, p, clamp01=True), R); report(f"ssim_fwd @{S}", ms, 0, 8 * n)
+        ms = timeit(lambda: ops.psnr(p, g, clamp01=True), R); report(f"psnr @{S}", ms, 0, 8 * n)
+        for tag, x in (("B,1", pred), ("B,5 ensemble", ens)):
+            M.calc_metrics(x, tgt)
+            ts = []
+            for _ in range(R):   # host clock: calc_metrics ends in its one device-to-host copy
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                M.calc_metrics(x, tgt)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            report(f"calc_metrics (56 keys, host clock) {tag} @{S}", sorted(ts)[len(ts) // 2], 0, 4 * (x.numel() + n))
     print("---- per-step totals (ms), weighted by layer multiplicity ----")
     for k, v in tot.items():
         print(f"{k:14s} {v:9.2f}")

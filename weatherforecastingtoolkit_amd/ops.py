@@ -1440,6 +1440,57 @@ def psnr(pred, target, clamp01=False):
     return out
 
 
+# ------------------------------------------------------- forecast-skill scores (csrc/skill.hip)
+POOL_TYPES = {"none": 0, "avg": 1, "max": 2}
+
+
+def skill_scores(pred, target, thresholds, pools, clamp01=False):
+    """Contingency counts and CRPS sums of pipeline/metrics.py:9-68 in one pass.
+
+    pred (B, T, C, H, W) or an ensemble (B, N, T, C, H, W), target (B, T, C, H, W), both fp32; thresholds: up to 8
+    floats (compared in fp32, like `tensor >= python_float`); pools: up to 3 (type, scale) pairs, type in
+    'none' / 'avg' / 'max'.  -> int64 device tensor (len(pools), 3 * len(thresholds) + 2): per pool [tp, fn, fp] per
+    threshold (on the ensemble mean), the CRPS sum over pooled cells as the bits of a float64, the pooled cell count."""
+    import ctypes
+    _chk(pred, target)
+    if pred.dim() == 5:
+        b, t, c, h, w = pred.shape
+        n = 1
+    elif pred.dim() == 6:
+        b, n, t, c, h, w = pred.shape
+    else:
+        raise _lib.WfaeError(f"skill_scores: pred must be 5-D or 6-D, got {tuple(pred.shape)}")
+    if tuple(target.shape) != (b, t, c, h, w):
+        raise _lib.WfaeError(f"skill_scores: target {tuple(target.shape)} does not match pred {tuple(pred.shape)}")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise _lib.WfaeError("skill_scores: fp32 tensors only")
+    if not (pred.is_contiguous() and target.is_contiguous()):
+        raise _lib.WfaeError("skill_scores: contiguous tensors only")
+    thr = (ctypes.c_float * max(1, len(thresholds)))(*[float(x) for x in thresholds])
+    types = (ctypes.c_int * max(1, len(pools)))(*[POOL_TYPES[p] for p, _ in pools])
+    scales = (ctypes.c_int * max(1, len(pools)))(*[int(s) for _, s in pools])
+    out = torch.empty((len(pools), 3 * len(thresholds) + 2), dtype=torch.int64, device=pred.device)
+    ws = workspace()
+    _call("wfae_skill_scores", 0, 4 * (pred.numel() + target.numel()), _p(pred), _p(target), _p(out), b, n, t * c, h,
+          w, ctypes.addressof(thr), len(thresholds), ctypes.addressof(types), ctypes.addressof(scales), len(pools),
+          int(clamp01), ws.data_ptr(), ws.numel(), _stream())
+    return out
+
+
+def ensemble_mean(pred, clamp01=False):
+    """pred (B, N, ...) -> (B, ...): pred.mean(dim=1) in torch's order (sequential sum over N, then / N); clamp01
+    clamps every member to [0, 1] first."""
+    _chk(pred)
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() < 2:
+        raise _lib.WfaeError("ensemble_mean: contiguous fp32 tensor (B, N, ...) only")
+    b, n = pred.shape[:2]
+    out = torch.empty((b,) + tuple(pred.shape[2:]), dtype=torch.float32, device=pred.device)
+    inner = out.numel() // b
+    _call("wfae_ensemble_mean", 0, 4 * (pred.numel() + out.numel()), _p(pred), _p(out), b, n, inner, int(clamp01),
+          _stream())
+    return out
+
+
 # ------------------------------------------------------- latent transformer
 def layernorm_fwd(x, res, gamma, beta, eps=1e-5):
     _chk(x, res, gamma, beta)
