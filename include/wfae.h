@@ -535,6 +535,38 @@ int wfae_mse_fwd(const float* pred, const float* target, float* loss, int64_t n,
 int wfae_mse_bwd(const float* pred, const float* target, const float* gloss, float* dpred, int64_t n,
                  wfae_stream_t stream);
 
+/* ---- DLinear latent forecasters (reference experiments/v1_experiments/
+ * pretrained_ae_dlinear_{sevir,ind,indc_indp}/train.py:22-100 `moving_avg`, `series_decomp`, `DLinear`).
+ * v (B, R, M): R rows per batch element, M columns; the predictor reads rows [0, L).  diff != 0 first subtracts the
+ *   last input frame: row r -> row r - row (L - cf + r % cf) (`inp - inp_t`, cf = features per time step).
+ * Decomposition along L with replicate padding of (K-1)/2 rows at each end: trend = AvgPool1d(K, stride 1),
+ *   seasonal = x - trend.  K must be odd (K > L allowed).
+ * dlinear_fwd: y (B, P, M) = Ws seasonal + bs + Wt trend + bt per column; individual != 0: W (M, P, L), b (M, P),
+ *   else W (P, L), b (P) shared by all columns.
+ * dlinear_bwd_weight: dWs = sum_b dy (x) seasonal, dWt likewise with trend, dbs = dbt = sum_b dy (summed over the
+ *   columns too for shared weights: block partials + a fixed-order finalize, ws >= ceil(M/64) (2PL+P) floats).
+ *   Outputs are overwritten; results are bitwise repeatable.
+ * dlinear_bwd_data: dv (B, R, M) through the transposed decomposition (and the differencing); rows >= L are zero.
+ *   ws >= 2 B L M floats.
+ * series_decomp_fwd / _bwd: x (B, L, M) <-> (seasonal, trend).
+ * dlinear_frames: mode 0 (target) out (B, P, M) = v[:, L + p] - v[:, L - cf + p % cf] (R >= L + P);
+ *   mode 1 (forecast) out = a + v[:, L - cf + p % cf]  (`pred + inp_t`, the (B, Tout, C, h, w) latent layout). */
+int wfae_dlinear_fwd(const float* v, const float* w_seasonal, const float* b_seasonal, const float* w_trend,
+                     const float* b_trend, float* y, int B, int R, int M, int L, int P, int K, int individual, int diff,
+                     int cf, wfae_stream_t stream);
+int wfae_dlinear_bwd_weight(const float* v, const float* dy, float* dw_seasonal, float* db_seasonal, float* dw_trend,
+                            float* db_trend, int B, int R, int M, int L, int P, int K, int individual, int diff, int cf,
+                            void* ws, size_t ws_bytes, wfae_stream_t stream);
+int wfae_dlinear_bwd_data(const float* dy, const float* w_seasonal, const float* w_trend, float* dv, int B, int R,
+                          int M, int L, int P, int K, int individual, int diff, int cf, void* ws, size_t ws_bytes,
+                          wfae_stream_t stream);
+int wfae_series_decomp_fwd(const float* x, float* seasonal, float* trend, int B, int L, int M, int K,
+                           wfae_stream_t stream);
+int wfae_series_decomp_bwd(const float* dseasonal, const float* dtrend, float* dx, int B, int L, int M, int K,
+                           wfae_stream_t stream);
+int wfae_dlinear_frames(const float* a, const float* v, float* out, int B, int R, int M, int L, int P, int cf, int mode,
+                        wfae_stream_t stream);
+
 /* ---- sigmoid + L1 loss (ae_64x8x8_lin.py:102 + experiments/ae_v2/train.py:55)
  * recon = sigmoid(h); loss[0] = weight * mean |recon - x|  (fp64 accumulation).
  * bwd: dh = gloss[0] * weight * sign(recon-x) * recon*(1-recon) / n */

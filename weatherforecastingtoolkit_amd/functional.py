@@ -1146,3 +1146,64 @@ def l1_loss(recon, x, weight=1.0):
 
 def ssim(x, y):
     return SsimFn.apply(x, y)
+
+
+class DLinearFn(Function):
+    """DLinear of the reference's v1 experiments (pretrained_ae_dlinear_*/train.py:50-100) on the column layout:
+    v (B, R, M) -> y (B, P, M) = Ws seasonal + bs + Wt trend + bt of rows [0, L) of v, seasonal / trend the
+    replicate-padded moving-average decomposition with window K.  Weights are stacked (M, P, L) when individual,
+    else shared (P, L).  diff: the rows are first differenced against the last input frame (L - cf + r % cf), the
+    reference's `inp - inp_t`.  The input gradient is formed only when v requires one."""
+
+    @staticmethod
+    def forward(ctx, v, ws, bs, wt, bt, L, K, individual, diff, cf):
+        v = _c(v)
+        P = bs.shape[-1]
+        y = ops.dlinear_fwd(v, ws, bs, wt, bt, L, P, K, individual, diff, cf)
+        ctx.save_for_backward(v, ws, wt)
+        ctx.cfg = (L, P, K, individual, diff, cf)
+        ctx.biases = (bs, bt)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        v, ws, wt = ctx.saved_tensors
+        L, P, K, individual, diff, cf = ctx.cfg
+        bs, bt = ctx.biases
+        dy = _c(dy)
+        dws, dwt, dbs, dbt = grad_buffer(ws), grad_buffer(wt), grad_buffer(bs), grad_buffer(bt)
+        ops.dlinear_bwd_weight(v, dy, dws, dbs, dwt, dbt, L, P, K, individual, diff, cf)
+        dv = None
+        if ctx.needs_input_grad[0]:
+            dv = ops.dlinear_bwd_data(dy, ws, wt, v.shape[1], L, K, individual, diff, cf)
+        return dv, dws, dbs, dwt, dbt, None, None, None, None, None
+
+
+def dlinear(v, ws, bs, wt, bt, L, K, individual, diff=False, cf=1):
+    return DLinearFn.apply(v, ws, bs, wt, bt, L, K, bool(individual), bool(diff), int(cf))
+
+
+class SeriesDecompFn(Function):
+    """series_decomp (pretrained_ae_dlinear_*/train.py:38-48): x (B, L, M) -> (x - trend, trend), trend the
+    replicate-padded AvgPool1d(K, stride 1) along L"""
+
+    @staticmethod
+    def forward(ctx, x, K):
+        ctx.K = K
+        return ops.series_decomp_fwd(_c(x), K)
+
+    @staticmethod
+    def backward(ctx, ds, dt):
+        ds = _c(ds) if ds is not None else None
+        dt = _c(dt) if dt is not None else None
+        if ds is None:
+            ds = torch.zeros_like(dt)
+        if dt is None:
+            dt = torch.zeros_like(ds)
+        return ops.series_decomp_bwd(ds, dt, ctx.K), None
+
+
+def series_decomp(x, K):
+    if K < 1 or K % 2 == 0:
+        raise ops._lib.WfaeError(f"series_decomp: kernel_size must be odd and >= 1, got {K}")
+    return SeriesDecompFn.apply(x, K)

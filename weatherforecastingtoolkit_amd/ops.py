@@ -1410,6 +1410,88 @@ def mse_bwd(pred, target, gloss):
     return d
 
 
+# ---- DLinear (include/wfae.h "DLinear latent forecasters"): v (B, R, M), the predictor reads rows [0, L) ----------
+def _dl_dims(v, L, P, K, individual, w):
+    b, r, m = v.shape
+    if K < 1 or K % 2 == 0:
+        raise _lib.WfaeError(f"dlinear: kernel_size must be odd and >= 1, got {K}")
+    want = (m, P, L) if individual else (P, L)
+    if tuple(w.shape) != want:
+        raise _lib.WfaeError(f"dlinear: weight shape {tuple(w.shape)}, expected {want}")
+    return b, r, m
+
+
+def dlinear_fwd(v, ws, bs, wt, bt, L, P, K, individual, diff=False, cf=1):
+    """-> y (B, P, M) = Ws seasonal + bs + Wt trend + bt of rows [0, L) of v (differenced against the last input
+    frame when diff)"""
+    _chk(v, ws, bs, wt, bt)
+    b, r, m = _dl_dims(v, L, P, K, individual, ws)
+    y = torch.empty((b, P, m), dtype=torch.float32, device=v.device)
+    nbytes = 4 * (b * L * m + b * P * m + 2 * ws.numel() + 2 * bs.numel())
+    _call("wfae_dlinear_fwd", 4 * b * m * P * L, nbytes, _p(v), _p(ws), _p(bs), _p(wt), _p(bt), _p(y), b, r, m, L, P,
+          K, int(individual), int(diff), cf, _stream())
+    return y
+
+
+def dlinear_bwd_weight(v, dy, dws, dbs, dwt, dbt, L, P, K, individual, diff=False, cf=1):
+    """dWs, dbs, dWt, dbt (overwritten) of dlinear_fwd for the output gradient dy (B, P, M)"""
+    _chk(v, dy, dws, dbs, dwt, dbt)
+    b, r, m = _dl_dims(v, L, P, K, individual, dws)
+    ws = workspace(4 * ((m + 63) // 64) * (2 * P * L + P))
+    nbytes = 4 * (b * L * m + b * P * m + 2 * dws.numel() + 2 * dbs.numel())
+    _call("wfae_dlinear_bwd_weight", 4 * b * m * P * L, nbytes, _p(v), _p(dy), _p(dws), _p(dbs), _p(dwt), _p(dbt),
+          b, r, m, L, P, K, int(individual), int(diff), cf, ws.data_ptr(), ws.numel(), _stream())
+
+
+def dlinear_bwd_data(dy, ws_, wt, R, L, K, individual, diff=False, cf=1):
+    """-> dv (B, R, M): the input gradient of dlinear_fwd (rows >= L are zero)"""
+    _chk(dy, ws_, wt)
+    b, P, m = dy.shape
+    if tuple(ws_.shape) != ((m, P, L) if individual else (P, L)):
+        raise _lib.WfaeError(f"dlinear_bwd_data: weight shape {tuple(ws_.shape)} does not match dy {tuple(dy.shape)}")
+    dv = torch.empty((b, R, m), dtype=torch.float32, device=dy.device)
+    w = workspace(8 * b * L * m)
+    _call("wfae_dlinear_bwd_data", 4 * b * m * P * L, 4 * (b * P * m + 2 * ws_.numel() + b * R * m), _p(dy), _p(ws_),
+          _p(wt), _p(dv), b, R, m, L, P, K, int(individual), int(diff), cf, w.data_ptr(), w.numel(), _stream())
+    return dv
+
+
+def series_decomp_fwd(x, K):
+    """x (B, L, M) -> (seasonal, trend) along L"""
+    _chk(x)
+    b, L, m = x.shape
+    s, t = torch.empty_like(x), torch.empty_like(x)
+    _call("wfae_series_decomp_fwd", 0, 12 * x.numel(), _p(x), _p(s), _p(t), b, L, m, K, _stream())
+    return s, t
+
+
+def series_decomp_bwd(ds, dt, K):
+    _chk(ds, dt)
+    b, L, m = ds.shape
+    dx = torch.empty_like(ds)
+    _call("wfae_series_decomp_bwd", 0, 12 * ds.numel(), _p(ds), _p(dt), _p(dx), b, L, m, K, _stream())
+    return dx
+
+
+def dlinear_target(v, L, P, cf=1):
+    """v (B, R, M) -> (B, P, M) = v[:, L + p] - v[:, L - cf + p % cf]"""
+    _chk(v)
+    b, r, m = v.shape
+    out = torch.empty((b, P, m), dtype=torch.float32, device=v.device)
+    _call("wfae_dlinear_frames", 0, 12 * out.numel(), None, _p(v), _p(out), b, r, m, L, P, cf, 0, _stream())
+    return out
+
+
+def dlinear_forecast(pred, v, L, cf=1):
+    """pred (B, P, M) + the last input frame of v (B, R, M) -> (B, P, M)"""
+    _chk(pred, v)
+    b, P, m = pred.shape
+    out = torch.empty_like(pred)
+    _call("wfae_dlinear_frames", 0, 12 * out.numel(), _p(pred), _p(v), _p(out), b, v.shape[1], m, L, P, cf, 1,
+          _stream())
+    return out
+
+
 def ssim_fwd(x, y, clamp01=False):
     _chk(x, y)
     nb = x.shape[0] * x.shape[1]
