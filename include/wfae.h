@@ -567,6 +567,35 @@ int wfae_series_decomp_bwd(const float* dseasonal, const float* dtrend, float* d
 int wfae_dlinear_frames(const float* a, const float* v, float* out, int B, int R, int M, int L, int P, int cf, int mode,
                         wfae_stream_t stream);
 
+/* ---- conv latent autoencoder (reference experiments/v1_experiments/pretrained_ae_convae_sevir/train.py:58-143
+ * `ConvEncoder`, `ConvDecoder`, `ConvModel`; :155 `nn.HuberLoss`).
+ * The fused unit ("CLN"): y (N, Cout, Ho, Wo) = LeakyReLU_slope(LN(conv(x) + bias) * gamma + beta), x (N, Cin, H, W).
+ *   kind 0: Conv2d 3x3 stride 1 pad 1 (Ho = H), w (Cout, Cin, 3, 3); kind 1: Conv2d 4x4 stride 2 pad 1 (Ho = H / 2, H and
+ *   W even), w (Cout, Cin, 4, 4); kind 2: ConvTranspose2d 4x4 stride 2 pad 1 (Ho = 2 H), w (Cin, Cout, 4, 4).
+ *   LN = nn.LayerNorm([Cout, Ho, Wo]): mean and biased variance per sample over E = Cout Ho Wo elements (two passes),
+ *   eps 1e-5, gamma / beta (Cout, Ho, Wo) per element.  LeakyReLU: a > 0 ? a : slope * a.
+ *   Served: Cin <= 64, Cout <= 16, E <= 18432 (one workgroup holds a sample's pre-norm output in LDS); anything else
+ *   returns WFAE_ERR_UNSUPPORTED / WFAE_ERR_BAD_SHAPE.
+ * cln_fwd writes y and, for the backward, xhat (N, Cout, Ho, Wo) = the normalised pre-affine value, mean (N), rstd (N).
+ *   The pre-norm convolution output is never stored.
+ * cln_bwd: from dy, xhat, rstd, gamma, beta (the mask is recomputed from a = gamma xhat + beta: a > 0 ? 1 : slope, as
+ *   EW_LRELU_BWD), x and w: dx (N, Cin, H, W) (skipped when dx is null), dw, dbias (Cout), dgamma, dbeta (Cout, Ho, Wo).
+ *   All outputs are overwritten.  ws >= N (|w| + Cout) floats: per-sample partials of dw and dbias, summed over the
+ *   samples in ascending order by a finalize kernel, like dgamma / dbeta.  No atomics: results are bitwise repeatable.
+ * huber: loss = mean of 0.5 d^2 (|d| <= delta) or delta (|d| - 0.5 delta), d = pred - target (fp64 partials, fixed-order
+ *   finalize, ws >= 1024 doubles); dpred = gloss * clamp(d, -delta, delta) / n. */
+int wfae_cln_fwd(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, float* y,
+                 float* xhat, float* mean, float* rstd, int kind, int N, int Cin, int Cout, int H, int W, float slope,
+                 wfae_stream_t stream);
+int wfae_cln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, const float* beta,
+                 const float* x, const float* w, float* dx, float* dw, float* dbias, float* dgamma, float* dbeta,
+                 int kind, int N, int Cin, int Cout, int H, int W, float slope, void* ws, size_t ws_bytes,
+                 wfae_stream_t stream);
+int wfae_huber_fwd(const float* pred, const float* target, float* loss, int64_t n, float delta, void* ws,
+                   size_t ws_bytes, wfae_stream_t stream);
+int wfae_huber_bwd(const float* pred, const float* target, const float* gloss, float* dpred, int64_t n, float delta,
+                   wfae_stream_t stream);
+
 /* ---- sigmoid + L1 loss (ae_64x8x8_lin.py:102 + experiments/ae_v2/train.py:55)
  * recon = sigmoid(h); loss[0] = weight * mean |recon - x|  (fp64 accumulation).
  * bwd: dh = gloss[0] * weight * sign(recon-x) * recon*(1-recon) / n */
@@ -672,6 +701,13 @@ int wfae_sq_attn_bwd(const float* q, const float* kv, const float* probs, const 
 int wfae_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
                float grad_scale, wfae_stream_t stream);
+/* The same with the complements 1 - beta1 and 1 - beta2 passed in: torch forms them from the Python doubles and rounds
+ * once, while 1.f - 0.999f is 1.3e-5 short of 0.001, which scales every step by 1 + 6.4e-6 (visible on parameters that
+ * start at zero, such as biases).  wfae_adamw keeps forming them in fp32 from the rounded betas and is what
+ * FusedAdamW calls unless it is built with exact_complements=True. */
+int wfae_adamw_c(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                 float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay, float bias_corr1,
+                 float bias_corr2, float grad_scale, wfae_stream_t stream);
 /* out[0] = sum x^2 (fp64 accumulation, written as fp64): grad-norm tracking
  * (pipeline/helpers.py:250-256) */
 int wfae_sumsq(const float* x, int64_t n, double* out, void* ws, size_t ws_bytes,

@@ -583,6 +583,27 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   }
 }
 
+// adamw_kernel with 1 - beta1 and 1 - beta2 handed in (wfae_adamw_c): formed by the caller in double and rounded once, as
+// torch does.  adamw_kernel keeps its own fp32 complements, so what it computes does not change.
+__global__ __launch_bounds__(256) void adamw_c_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                      float* __restrict__ m, float* __restrict__ v, long n, float lr,
+                                                      float b2, float omb1, float omb2, float eps, float wd, float bc1,
+                                                      float bc2_sqrt, float gscale) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  const float step = lr / bc1;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float gv = g[i] * gscale;
+    float pv = p[i];
+    pv *= 1.f - lr * wd;
+    const float mv = m[i] + (gv - m[i]) * omb1;
+    const float vv = b2 * v[i] + omb2 * gv * gv;
+    m[i] = mv;
+    v[i] = vv;
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    p[i] = pv - step * (mv / denom);
+  }
+}
+
 __global__ void vil_u8_to_f32_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int H, int W, int T,
                                      float scale, long total) {
   // dst[n][t][h][w] = scale * src[n][h][w][t]
@@ -1082,6 +1103,19 @@ int wfae_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr,
                      beta1, beta2, eps, weight_decay, bias_corr1, sqrtf(bias_corr2), grad_scale);
   return check_launch("adamw");
+}
+
+int wfae_adamw_c(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                 float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay, float bias_corr1,
+                 float bias_corr2, float grad_scale, wfae_stream_t stream) {
+  WFAE_REQUIRE(p && g && m && v, WFAE_ERR_NULL_POINTER, "adamw_c: null pointer");
+  WFAE_REQUIRE(n >= 0, WFAE_ERR_BAD_SHAPE, "adamw_c: bad size");
+  (void)beta1;   // only its complement enters the lerp form of the first moment
+  if (n == 0) return WFAE_OK;
+  hipLaunchKernelGGL(adamw_c_kernel, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr,
+                     beta2, one_minus_beta1, one_minus_beta2, eps, weight_decay, bias_corr1, sqrtf(bias_corr2),
+                     grad_scale);
+  return check_launch("adamw_c");
 }
 
 int wfae_sumsq(const float* x, int64_t n, double* out, void* ws, size_t ws_bytes, wfae_stream_t stream) {

@@ -1207,3 +1207,51 @@ def series_decomp(x, K):
     if K < 1 or K % 2 == 0:
         raise ops._lib.WfaeError(f"series_decomp: kernel_size must be odd and >= 1, got {K}")
     return SeriesDecompFn.apply(x, K)
+
+
+class ConvLayerNormActFn(Function):
+    """one unit of the conv latent autoencoder (reference v1_experiments/pretrained_ae_convae_sevir/train.py:62-108):
+    LeakyReLU_slope(LayerNorm([C, H, W])(conv(x) + bias)) in one launch per sample batch (csrc/convae.hip); kind 0 =
+    Conv2d 3x3 pad 1, 1 = Conv2d 4x4 stride 2 pad 1, 2 = ConvTranspose2d 4x4 stride 2 pad 1.  Saved for backward: x,
+    x_hat and rstd (the pre-norm convolution output is never stored).  The data gradient is formed only when x
+    requires one."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, gamma, beta, kind, slope):
+        x = _c(x)
+        y, xhat, _, rstd = ops.cln_fwd(x, w, bias, gamma, beta, kind, slope)
+        ctx.save_for_backward(x, w, gamma, beta, xhat, rstd)
+        ctx.bias, ctx.kind, ctx.slope = bias, kind, slope
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, gamma, beta, xhat, rstd = ctx.saved_tensors
+        dw, db, dg, dbt = grad_buffer(w), grad_buffer(ctx.bias), grad_buffer(gamma), grad_buffer(beta)
+        dx = ops.cln_bwd(_c(dy), xhat, rstd, gamma, beta, x, w, dw, db, dg, dbt, ctx.kind, ctx.slope,
+                         need_dx=ctx.needs_input_grad[0])
+        return dx, dw, db, dg, dbt, None, None
+
+
+def conv_layernorm_act(x, w, bias, gamma, beta, kind, slope=0.01):
+    return ConvLayerNormActFn.apply(x, w, bias, gamma, beta, int(kind), float(slope))
+
+
+class HuberLossFn(Function):
+    """nn.HuberLoss(delta) with mean reduction (reference pretrained_ae_convae_sevir/train.py:155)"""
+
+    @staticmethod
+    def forward(ctx, pred, target, delta):
+        pred, target = _c(pred), _c(target)
+        ctx.save_for_backward(pred, target)
+        ctx.delta = delta
+        return ops.huber_fwd(pred, target, delta)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target = ctx.saved_tensors
+        return ops.huber_bwd(pred, target, _c(g), ctx.delta), None, None
+
+
+def huber_loss(pred, target, delta=1.0):
+    return HuberLossFn.apply(pred, target, float(delta))

@@ -1492,6 +1492,78 @@ def dlinear_forecast(pred, v, L, cf=1):
     return out
 
 
+# ---- conv latent autoencoder (include/wfae.h "conv latent autoencoder"): the fused conv + LayerNorm + LeakyReLU unit
+CLN_KINDS = {"conv3": 0, "down4": 1, "up4": 2}
+
+
+def _cln_dims(x, w, kind):
+    if kind not in (0, 1, 2):
+        raise _lib.WfaeError(f"cln: kind {kind!r}, expected 0 (3x3 s1), 1 (4x4 s2) or 2 (transposed 4x4 s2)")
+    n, cin, h, wd = x.shape
+    k = 3 if kind == 0 else 4
+    cout = w.shape[1] if kind == 2 else w.shape[0]
+    want = (cin, cout, k, k) if kind == 2 else (cout, cin, k, k)
+    if tuple(w.shape) != want:
+        raise _lib.WfaeError(f"cln: weight shape {tuple(w.shape)}, expected {want} for input {tuple(x.shape)}")
+    if kind == 1 and (h % 2 or wd % 2):
+        raise _lib.WfaeError(f"cln: the 4x4 stride-2 convolution needs an even input plane, got {h}x{wd}")
+    ho, wo = (h, wd) if kind == 0 else (h // 2, wd // 2) if kind == 1 else (2 * h, 2 * wd)
+    return n, cin, cout, h, wd, ho, wo, k
+
+
+def cln_fwd(x, w, bias, gamma, beta, kind, slope=0.01):
+    """-> y, xhat (N, Cout, Ho, Wo), mean, rstd (N): LeakyReLU_slope(LayerNorm([Cout, Ho, Wo])(conv(x) + bias))"""
+    _chk(x, w, bias, gamma, beta)
+    n, cin, cout, h, wd, ho, wo, k = _cln_dims(x, w, kind)
+    if tuple(gamma.shape) != (cout, ho, wo) or tuple(beta.shape) != (cout, ho, wo):
+        raise _lib.WfaeError(f"cln_fwd: LayerNorm affine {tuple(gamma.shape)}, expected {(cout, ho, wo)}")
+    y = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=x.device)
+    xhat = torch.empty_like(y)
+    mean = torch.empty((n,), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    e = cout * ho * wo
+    flops = 2 * n * e * cin * k * k // (4 if kind == 2 else 1) + 10 * n * e
+    _call("wfae_cln_fwd", flops, 4 * (x.numel() + w.numel() + 2 * e + 2 * n * e), _p(x), _p(w), _p(bias), _p(gamma),
+          _p(beta), _p(y), _p(xhat), _p(mean), _p(rstd), kind, n, cin, cout, h, wd, float(slope), _stream())
+    return y, xhat, mean, rstd
+
+
+def cln_bwd(dy, xhat, rstd, gamma, beta, x, w, dw, dbias, dgamma, dbeta, kind, slope=0.01, need_dx=True):
+    """dw, dbias, dgamma, dbeta are overwritten; -> dx (N, Cin, H, W) or None"""
+    _chk(dy, xhat, rstd, gamma, beta, x, w, dw, dbias, dgamma, dbeta)
+    n, cin, cout, h, wd, ho, wo, k = _cln_dims(x, w, kind)
+    if tuple(dy.shape) != (n, cout, ho, wo) or dy.shape != xhat.shape:
+        raise _lib.WfaeError(f"cln_bwd: dy {tuple(dy.shape)} / xhat {tuple(xhat.shape)}, expected {(n, cout, ho, wo)}")
+    dx = torch.empty_like(x) if need_dx else None
+    ws = workspace(4 * n * (w.numel() + cout))
+    e = cout * ho * wo
+    per = 2 * n * e * cin * k * k // (4 if kind == 2 else 1)
+    _call("wfae_cln_bwd", per * (2 if need_dx else 1) + 20 * n * e,
+          4 * (3 * n * e + 2 * x.numel() + 2 * w.numel() + 4 * e + 2 * n * w.numel()), _p(dy), _p(xhat), _p(rstd),
+          _p(gamma), _p(beta), _p(x), _p(w), _p(dx), _p(dw), _p(dbias), _p(dgamma), _p(dbeta), kind, n, cin, cout, h, wd,
+          float(slope), ws.data_ptr(), ws.numel(), _stream())
+    return dx
+
+
+def huber_fwd(pred, target, delta=1.0):
+    _chk(pred, target)
+    if pred.shape != target.shape:
+        raise _lib.WfaeError(f"huber_fwd: shapes {tuple(pred.shape)} and {tuple(target.shape)} differ")
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    ws = workspace()
+    _call("wfae_huber_fwd", 0, 8 * pred.numel(), _p(pred), _p(target), _p(loss), pred.numel(), float(delta), ws.data_ptr(),
+          ws.numel(), _stream())
+    return loss
+
+
+def huber_bwd(pred, target, gloss, delta=1.0):
+    _chk(pred, target, gloss)
+    d = torch.empty_like(pred)
+    _call("wfae_huber_bwd", 0, 12 * pred.numel(), _p(pred), _p(target), _p(gloss), _p(d), pred.numel(), float(delta),
+          _stream())
+    return d
+
+
 def ssim_fwd(x, y, clamp01=False):
     _chk(x, y)
     nb = x.shape[0] * x.shape[1]
@@ -1696,8 +1768,14 @@ def dropout(x, p_drop, seed):
 
 
 # ---------------------------------------------------------------- optimiser
-def adamw_(p, g, m, v, lr, beta1, beta2, eps, wd, bc1, bc2, grad_scale=1.0):
+def adamw_(p, g, m, v, lr, beta1, beta2, eps, wd, bc1, bc2, grad_scale=1.0, exact_complements=False):
+    """exact_complements: 1 - beta formed from the Python doubles and rounded once, as torch does (wfae_adamw_c); the
+    default forms them in fp32 from the rounded betas (1.f - 0.999f is 1.3e-5 short of 0.001)"""
     _chk(p, g, m, v)
+    if exact_complements:
+        _call("wfae_adamw_c", 0, 28 * p.numel(), _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, 1.0 - beta1,
+              1.0 - beta2, eps, wd, bc1, bc2, grad_scale, _stream(), label="wfae_adamw")
+        return
     _call("wfae_adamw", 0, 28 * p.numel(), _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, wd, bc1, bc2, grad_scale,
               _stream())
 

@@ -75,11 +75,17 @@ class FlatArena:
 
 class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW semantics (eps 1e-8, decoupled weight decay, no amsgrad),
-    one wfae_adamw launch per parameter group when all gradients sit in the arena."""
+    one wfae_adamw launch per parameter group when all gradients sit in the arena.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, flatten=True):
+    exact_complements=True forms 1 - beta1 and 1 - beta2 in double and rounds once, as torch does (wfae_adamw_c).  The
+    default keeps the fp32 complements of the rounded betas (1.f - 0.999f is 1.3e-5 short of 0.001, every step 6.4e-6
+    larger than torch's — visible only on parameters that start at zero), so existing runs reproduce."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, flatten=True,
+                 exact_complements=False):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
+        self.exact_complements = bool(exact_complements)
         self.grad_scale = 1.0  # set to 1/world_size by the data-parallel wrapper
         self._arenas = []
         for g in self.param_groups:
@@ -178,7 +184,7 @@ class FusedAdamW(torch.optim.Optimizer):
             t = g["step"]
             b1, b2 = g["betas"]
             bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
-            args = (g["lr"], b1, b2, g["eps"], g["weight_decay"], bc1, bc2, self.grad_scale)
+            args = (g["lr"], b1, b2, g["eps"], g["weight_decay"], bc1, bc2, self.grad_scale, self.exact_complements)
             if arena is not None:
                 runs, stray = arena.runs()
                 for a, b in runs:  # one launch per contiguous run (one run when every parameter has a grad)

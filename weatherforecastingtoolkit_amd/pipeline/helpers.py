@@ -12,10 +12,11 @@ from .. import ops
 from ..optim import CosineWarmupLR, FusedAdamW
 
 
-def adamw_optimizer(model, lr, weight_decay, beta1=0.9, beta2=0.999):
+def adamw_optimizer(model, lr, weight_decay, beta1=0.9, beta2=0.999, exact_complements=False):
     """reference pipeline/helpers.py:63-74 -> torch.optim.AdamW(model.parameters(), ...);
-    here one fused kernel over a flat parameter arena with identical arithmetic."""
-    return FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, betas=(beta1, beta2))
+    here one fused kernel over a flat parameter arena with identical arithmetic (`exact_complements`: see FusedAdamW)."""
+    return FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, betas=(beta1, beta2),
+                      exact_complements=exact_complements)
 
 
 def cosine_warmup_scheduler(opt, start_lr, final_lr, peak_lr, total_steps, warmup_steps):
