@@ -596,6 +596,45 @@ int wfae_huber_fwd(const float* pred, const float* target, float* loss, int64_t 
 int wfae_huber_bwd(const float* pred, const float* target, const float* gloss, float* dpred, int64_t n, float delta,
                    wfae_stream_t stream);
 
+/* ---- frozen AutoencoderKL latent provider, forward only (reference pipeline/models/autoencoderkl/autoencoder_kl.py
+ * `AutoencoderKL`; vae.py `Encoder`, `Decoder`; resnet.py `ResnetBlock2D`, `Downsample2D`, `Upsample2D`; attention.py
+ * `AttentionBlock`; distributions.py `DiagonalGaussianDistribution`).  Added within ABI version 103; nothing changed.
+ * conv3: 3x3 convolution, NCHW fp32, implicit GEMM on the matrix cores with fp32 accumulation.
+ *   kind 0: stride 1, pad 1 (Ho = H).  kind 1: stride 2 over the input zero-padded (0, 1, 0, 1) (`Downsample2D` with
+ *   padding = 0; Ho = (H - 2) / 2 + 1).  kind 2: stride 1, pad 1 over the nearest x2 upsample of x (`Upsample2D` + conv;
+ *   Ho = 2 H) — the upsampled tensor is never written.
+ *   mode 3: operands as three exact bf16 planes, six v_mfma_f32_16x16x32_bf16 per product (fp32-exact; 'highest' /
+ *   'high').  mode 1: the h plane alone = operands rounded to bf16 ('medium').  mode 4: fp32 operands on
+ *   v_mfma_f32_16x16x4_f32 (fp32-exact; kept for the comparison in DESIGN.md).
+ *   The weights (Cout, Cin, 3, 3) are packed (and split) once with conv3_pack into conv3_pack_bytes bytes for a mode.
+ *   Prologue (gn_scale / gn_shift (N, Cin), both or neither): the operand is SiLU(x * scale + shift) — GroupNorm folded
+ *   by gn_stats — applied on the load; padding taps are zeros AFTER it.  Epilogue: y = (conv + bias (may be null) + res
+ *   (y's shape, may be null)) * out_mul.  Channel counts 1..4096 (padded to 32 / 64 inside); other arguments out of range
+ *   return WFAE_ERR_BAD_SHAPE / WFAE_ERR_UNSUPPORTED.
+ * gn_stats: GroupNorm statistics per (sample, group), biased variance, two-level fixed-order reduction of (mean, M2)
+ *   pairs in fp64 (no atomics, no E[x^2] - E[x]^2): mean, rstd (N, groups); scale = gamma rstd and
+ *   shift = beta - mean rstd gamma (N, C).  ws >= gn_ws_bytes.
+ * to_tokens: tok (N, S, C) = x (N, C, S) * scale + shift (scale / shift may both be null); from_tokens: y (N, C, S) =
+ *   (tok (N, S, C) + res (N, C, S) (may be null)) * mul.  C and S multiples of 32.
+ * softmax: y[row] = softmax(scale * x[row]) over `cols` (in place allowed).
+ * posterior: moments (N, 2C, HW) -> mean, logvar = clamp(., -30, 20), std = exp(logvar / 2), and — when noise and
+ *   sample are given — sample = mean + std * noise, all (N, C, HW). */
+size_t wfae_aekl_conv3_pack_bytes(int Cout, int Cin, int mode);
+int wfae_aekl_conv3_pack(const float* w, void* packed, int Cout, int Cin, int mode, wfae_stream_t stream);
+int wfae_aekl_conv3_fwd(const float* x, const void* packed, const float* bias, const float* gn_scale, const float* gn_shift,
+                        const float* res, float* y, int kind, int mode, int N, int Cin, int Cout, int H, int W,
+                        float out_mul, wfae_stream_t stream);
+size_t wfae_aekl_gn_ws_bytes(int N, int C, int HW, int groups);
+int wfae_aekl_gn_stats(const float* x, const float* gamma, const float* beta, float* mean, float* rstd, float* scale,
+                       float* shift, int N, int C, int HW, int groups, float eps, void* ws, size_t ws_bytes,
+                       wfae_stream_t stream);
+int wfae_aekl_to_tokens(const float* x, const float* scale, const float* shift, float* tok, int N, int C, int S,
+                        wfae_stream_t stream);
+int wfae_aekl_from_tokens(const float* tok, const float* res, float* y, int N, int C, int S, float mul, wfae_stream_t stream);
+int wfae_aekl_softmax(const float* x, float* y, int64_t rows, int cols, float scale, wfae_stream_t stream);
+int wfae_aekl_posterior(const float* moments, const float* noise, float* mean, float* logvar, float* std_, float* sample, int N,
+                        int C, int HW, wfae_stream_t stream);
+
 /* ---- sigmoid + L1 loss (ae_64x8x8_lin.py:102 + experiments/ae_v2/train.py:55)
  * recon = sigmoid(h); loss[0] = weight * mean |recon - x|  (fp64 accumulation).
  * bwd: dh = gloss[0] * weight * sign(recon-x) * recon*(1-recon) / n */

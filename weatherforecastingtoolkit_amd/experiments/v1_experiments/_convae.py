@@ -232,7 +232,7 @@ def main(here, default_mode, argv=None):
         total = args.max_steps
     cfg.trainer.total_train_steps = total
     torch.manual_seed(0)
-    model = Model(cfg, autoencoder=Autoencoder(size, cfg.autoencoder.kind)).to(dev).train()
+    model = Model(cfg, autoencoder=Autoencoder(size, cfg.autoencoder.kind, cfg.autoencoder)).to(dev).train()
     model.autoencoder.eval()
     step, t0 = 0, time.time()
     if args.mode == "test":

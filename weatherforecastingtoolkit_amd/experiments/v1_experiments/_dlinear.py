@@ -202,7 +202,7 @@ class Autoencoder(_LatentEncoder):
     frame space like the reference (:196-200)."""
 
     def can_decode(self):
-        return self.kind == "ae_64x8x8_lin.enc"
+        return self.kind in ("ae_64x8x8_lin.enc", "autoencoder_kl")
 
     @torch.no_grad()
     def decode(self, z):
@@ -211,6 +211,9 @@ class Autoencoder(_LatentEncoder):
             raise WfaeError(f"Autoencoder.decode: kind {self.kind!r} has no decoder")
         b, t = z.shape[:2]
         ae = self.autoencoder
+        if self.kind == "autoencoder_kl":
+            x = torch.cat([ae.decode(f) for f in self._chunks(z.reshape(b * t, *z.shape[2:]))])
+            return x.view(b, t, *x.shape[1:])
         x = ae.act(ae.dec(z.reshape(b * t, *z.shape[2:]).contiguous()))
         return x.view(b, t, *x.shape[1:])
 
@@ -340,7 +343,7 @@ def main(here, default_mode, argv=None):
         total = args.max_steps
     cfg.trainer.total_train_steps = total
     torch.manual_seed(0)
-    model = Model(cfg, autoencoder=Autoencoder(size, cfg.autoencoder.kind)).to(dev).train()
+    model = Model(cfg, autoencoder=Autoencoder(size, cfg.autoencoder.kind, cfg.autoencoder)).to(dev).train()
     model.autoencoder.eval()
     step, t0 = 0, time.time()
     if args.mode == "test":

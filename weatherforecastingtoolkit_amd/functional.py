@@ -1255,3 +1255,50 @@ class HuberLossFn(Function):
 
 def huber_loss(pred, target, delta=1.0):
     return HuberLossFn.apply(pred, target, float(delta))
+
+
+# ---- frozen AutoencoderKL latent provider: forward-only building blocks (csrc/aekl.hip).  No autograd Function: the
+# provider is frozen, and a tensor that asks for a gradient is refused instead of being answered without a graph.
+def _aekl_no_grad(what, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise ops._lib.WfaeError(f"{what} is forward only (the AutoencoderKL provider is frozen): call it under "
+                                 "torch.no_grad() or detach its input")
+
+
+def aekl_group_norm_stats(x, gamma, beta, groups, eps=1e-6):
+    """-> (mean, rstd, scale, shift) of nn.GroupNorm(groups, C, eps): ops.aekl_gn_stats"""
+    _aekl_no_grad("aekl_group_norm_stats", x)
+    return ops.aekl_gn_stats(_c(x.detach()), gamma.detach(), beta.detach(), int(groups), float(eps))
+
+
+def aekl_conv3x3(x, packed, cout, bias=None, gn=None, res=None, kind=0, out_mul=1.0, mode=None):
+    """3x3 convolution of the provider on the matrix cores, with the GroupNorm + SiLU prologue `gn` and the
+    bias / residual / scale epilogue: ops.aekl_conv3_fwd"""
+    _aekl_no_grad("aekl_conv3x3", x, res)
+    return ops.aekl_conv3_fwd(_c(x.detach()), packed, int(cout), None if bias is None else bias.detach(), gn,
+                              None if res is None else _c(res.detach()), int(kind), mode, float(out_mul))
+
+
+def aekl_attention(x, gn, wq, bq, wk, bk, wv, bv, wo, bo, rescale=1.0):
+    """single-head AttentionBlock on x (N, C, H, W) with the folded GroupNorm affine gn = (scale, shift):
+    (proj(softmax(q k^T / sqrt C) v) + x) / rescale.  The four products run on linear_fwd / split_gemm."""
+    _aekl_no_grad("aekl_attention", x)
+    x = _c(x.detach())
+    n, c, h, w = x.shape
+    s = h * w
+    planes = 1 if ops.get_float32_matmul_precision() == "medium" else 3
+    tok = ops.aekl_to_tokens(x, gn).view(n * s, c)
+    q = ops.linear_fwd(tok, wq.detach(), bq.detach()).view(n, s, c)
+    k = ops.linear_fwd(tok, wk.detach(), bk.detach()).view(n, s, c)
+    v = ops.linear_fwd(tok, wv.detach(), bv.detach()).view(n, s, c)
+    scores = ops.split_gemm(ops.split_bf16x3(q, planes), ops.split_bf16x3(k, planes), b_kind=1)   # (n, s, s)
+    probs = ops.aekl_softmax(scores, 1.0 / float(c) ** 0.5)
+    ctxv = ops.split_gemm(ops.split_bf16x3(probs, planes), ops.split_bf16x3(v, planes), b_kind=0)   # (n, s, c)
+    out = ops.linear_fwd(ctxv.view(n * s, c), wo.detach(), bo.detach()).view(n, s, c)
+    return ops.aekl_from_tokens(out, x.shape, x, 1.0 / float(rescale))
+
+
+def aekl_posterior(moments, noise=None):
+    """-> (mean, logvar, std, sample): ops.aekl_posterior"""
+    _aekl_no_grad("aekl_posterior", moments)
+    return ops.aekl_posterior(_c(moments.detach()), None if noise is None else _c(noise))

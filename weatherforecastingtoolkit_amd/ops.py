@@ -1564,6 +1564,138 @@ def huber_bwd(pred, target, gloss, delta=1.0):
     return d
 
 
+# ---- frozen AutoencoderKL latent provider (include/wfae.h "frozen AutoencoderKL"; csrc/aekl.hip), forward only
+AEKL_KINDS = {"conv": 0, "down": 1, "up": 2}
+AEKL_MODES = {"bf16": 1, "split3": 3, "fp32": 4}
+# 'highest' / 'high' run "split3": measured 0.354 ms against 0.511 ms for "fp32" on the 128-channel 128 x 128 layer
+# (DESIGN.md).  "fp32" is reachable only through an explicit `mode=` (tools/aekl_bench.py's comparison, one test).
+
+
+def aekl_mode():
+    """operand form of the 3x3 kernel under the current matmul precision"""
+    return AEKL_MODES["bf16" if _lib.load().wfae_get_matmul_precision() == 1 else "split3"]
+
+
+def _aekl_peak(mode):
+    return PEAK_FP32_MFMA if mode == 4 else _planes_peak(mode)
+
+
+def aekl_conv3_pack(w, mode=None):
+    """(Cout, Cin, 3, 3) -> the packed (and split) operand of aekl_conv3_fwd for `mode`; done once per frozen layer"""
+    _chk(w)
+    mode = aekl_mode() if mode is None else mode
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise _lib.WfaeError(f"aekl_conv3_pack: weight shape {tuple(w.shape)}, expected (Cout, Cin, 3, 3)")
+    cout, cin = w.shape[:2]
+    nbytes = _lib.load().wfae_aekl_conv3_pack_bytes(cout, cin, mode)
+    if nbytes == 0:
+        raise _lib.WfaeError(f"aekl_conv3_pack: unsupported Cout={cout} Cin={cin} mode={mode}")
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    _call("wfae_aekl_conv3_pack", 0, 4 * w.numel() + nbytes, _p(w), packed.data_ptr(), cout, cin, mode, _stream())
+    return packed
+
+
+def aekl_conv3_fwd(x, packed, cout, bias=None, gn=None, res=None, kind=0, mode=None, out_mul=1.0):
+    """3x3 convolution on the matrix cores.  kind 0: stride 1 pad 1; 1: stride 2 over the (0, 1, 0, 1)-padded input;
+    2: over the nearest x2 upsample.  gn = (scale, shift) (N, Cin): operand SiLU(x * scale + shift), zero padding after
+    it.  y = (conv + bias + res) * out_mul."""
+    mode = aekl_mode() if mode is None else mode
+    scale, shift = gn if gn is not None else (None, None)
+    _chk(x, bias, scale, shift, res)
+    if x.dim() != 4:
+        raise _lib.WfaeError(f"aekl_conv3_fwd: expected (N, C, H, W), got {tuple(x.shape)}")
+    if kind not in (0, 1, 2):
+        raise _lib.WfaeError(f"aekl_conv3_fwd: kind {kind!r}, expected 0 (stride 1), 1 (stride 2) or 2 (x2 upsample)")
+    n, cin, h, wd = x.shape
+    want = _lib.load().wfae_aekl_conv3_pack_bytes(cout, cin, mode)
+    if want == 0 or packed.dtype != torch.uint8 or packed.numel() != want or not packed.is_cuda:
+        raise _lib.WfaeError(f"aekl_conv3_fwd: packed weights do not belong to Cout={cout} Cin={cin} mode={mode}")
+    if kind == 1 and (h < 2 or wd < 2):
+        raise _lib.WfaeError(f"aekl_conv3_fwd: the stride-2 form needs a plane of at least 2x2, got {h}x{wd}")
+    ho, wo = (h, wd) if kind == 0 else ((h - 2) // 2 + 1, (wd - 2) // 2 + 1) if kind == 1 else (2 * h, 2 * wd)
+    if gn is not None and (tuple(scale.shape) != (n, cin) or tuple(shift.shape) != (n, cin)):
+        raise _lib.WfaeError(f"aekl_conv3_fwd: prologue scale / shift {tuple(scale.shape)}, expected {(n, cin)}")
+    if bias is not None and tuple(bias.shape) != (cout,):
+        raise _lib.WfaeError(f"aekl_conv3_fwd: bias {tuple(bias.shape)}, expected {(cout,)}")
+    if res is not None and tuple(res.shape) != (n, cout, ho, wo):
+        raise _lib.WfaeError(f"aekl_conv3_fwd: residual {tuple(res.shape)}, expected {(n, cout, ho, wo)}")
+    y = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=x.device)
+    _call("wfae_aekl_conv3_fwd", 2 * 9 * n * ho * wo * cin * cout,
+          4 * (x.numel() + y.numel() * (2 if res is not None else 1)) + want, _p(x), packed.data_ptr(), _p(bias), _p(scale),
+          _p(shift), _p(res), _p(y), kind, mode, n, cin, cout, h, wd, float(out_mul), _stream(),
+          label=f"wfae_aekl_conv3_fwd k{kind} {cin}->{cout} {ho}x{wo}", peak=_aekl_peak(mode))
+    return y
+
+
+def aekl_gn_stats(x, gamma, beta, groups, eps=1e-6):
+    """GroupNorm statistics of x (N, C, ...) -> mean, rstd (N, groups), scale = gamma rstd, shift = beta - mean rstd gamma
+    (N, C): the folded per-(sample, channel) affine its consumers apply"""
+    _chk(x, gamma, beta)
+    n, c = x.shape[:2]
+    hw = x.numel() // max(1, n * c)
+    if groups <= 0 or c % groups or tuple(gamma.shape) != (c,) or tuple(beta.shape) != (c,):
+        raise _lib.WfaeError(f"aekl_gn_stats: {c} channels, {groups} groups, affine {tuple(gamma.shape)}")
+    mean = torch.empty((n, groups), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    scale = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    shift = torch.empty_like(scale)
+    ws = workspace(_lib.load().wfae_aekl_gn_ws_bytes(n, c, hw, groups))
+    _call("wfae_aekl_gn_stats", 0, 8 * x.numel(), _p(x), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(scale), _p(shift), n, c,
+          hw, groups, float(eps), ws.data_ptr(), ws.numel(), _stream())
+    return mean, rstd, scale, shift
+
+
+def aekl_to_tokens(x, gn=None):
+    """x (N, C, H, W) -> tokens (N, H*W, C), optionally through the folded GroupNorm affine gn = (scale, shift)"""
+    scale, shift = gn if gn is not None else (None, None)
+    _chk(x, scale, shift)
+    n, c = x.shape[:2]
+    s = x.numel() // (n * c)
+    if c % 32 or s % 32:
+        raise _lib.WfaeError(f"aekl_to_tokens: C and S = H*W must be multiples of 32 (got C={c} S={s})")
+    tok = torch.empty((n, s, c), dtype=torch.float32, device=x.device)
+    _call("wfae_aekl_to_tokens", 0, 8 * x.numel(), _p(x), _p(scale), _p(shift), _p(tok), n, c, s, _stream())
+    return tok
+
+
+def aekl_from_tokens(tok, shape, res=None, mul=1.0):
+    """tokens (N, S, C) -> (tokens^T + res) * mul in the NCHW `shape`"""
+    _chk(tok, res)
+    n, s, c = tok.shape
+    if c % 32 or s % 32:
+        raise _lib.WfaeError(f"aekl_from_tokens: C and S must be multiples of 32 (got C={c} S={s})")
+    y = torch.empty(tuple(shape), dtype=torch.float32, device=tok.device)
+    if y.numel() != tok.numel() or (res is not None and res.shape != y.shape) or shape[0] != n or shape[1] != c:
+        raise _lib.WfaeError(f"aekl_from_tokens: tokens {tuple(tok.shape)} do not fill {tuple(shape)}")
+    _call("wfae_aekl_from_tokens", 0, 12 * tok.numel(), _p(tok), _p(res), _p(y), n, c, s, float(mul), _stream())
+    return y
+
+
+def aekl_softmax(x, scale=1.0):
+    """softmax(scale * x) over the last dimension"""
+    _chk(x)
+    cols = x.shape[-1]
+    y = torch.empty_like(x)
+    _call("wfae_aekl_softmax", 0, 8 * x.numel(), _p(x), _p(y), x.numel() // cols, cols, float(scale), _stream())
+    return y
+
+
+def aekl_posterior(moments, noise=None):
+    """moments (N, 2C, H, W) -> mean, logvar (clamped to [-30, 20]), std, sample = mean + std * noise (None without noise)"""
+    _chk(moments, noise)
+    n, c2, h, wd = moments.shape
+    if c2 % 2:
+        raise _lib.WfaeError(f"aekl_posterior: {c2} moment channels, expected an even count")
+    shp = (n, c2 // 2, h, wd)
+    if noise is not None and tuple(noise.shape) != shp:
+        raise _lib.WfaeError(f"aekl_posterior: noise {tuple(noise.shape)}, expected {shp}")
+    mean, logvar, std = (torch.empty(shp, dtype=torch.float32, device=moments.device) for _ in range(3))
+    sample = torch.empty_like(mean) if noise is not None else None
+    _call("wfae_aekl_posterior", 0, 4 * moments.numel() * 3, _p(moments), _p(noise), _p(mean), _p(logvar), _p(std),
+          _p(sample), n, c2 // 2, h * wd, _stream())
+    return mean, logvar, std, sample
+
+
 def ssim_fwd(x, y, clamp01=False):
     _chk(x, y)
     nb = x.shape[0] * x.shape[1]

@@ -1,0 +1,90 @@
+"""Frozen `AutoencoderKL` latent provider of the v1 experiments on MI355X (reference pipeline/models/autoencoderkl/
+autoencoder_kl.py): the reference's constructor keywords, state_dict keys / order / shapes and seeded initial values;
+`encode(x) -> DiagonalGaussianDistribution`, `decode(z)`, `forward(...)`.  Forward only: the parameters are frozen and an
+input that asks for a gradient is refused (WfaeError) rather than answered without a graph.  A reference checkpoint
+loads with `load_state_dict`."""
+from __future__ import annotations
+
+import torch
+import torch.nn as tnn
+
+from .... import ops
+from ...._lib import WfaeError
+from .distributions import DiagonalGaussianDistribution
+from .vae import Decoder, Encoder
+
+
+class AutoencoderKL(tnn.Module):
+    def __init__(self, in_channels=3, out_channels=3, down_block_types=("DownEncoderBlock2D",),
+                 up_block_types=("UpDecoderBlock2D",), block_out_channels=(64,), layers_per_block=1, act_fn="silu",
+                 latent_channels=4, norm_num_groups=32, sample_size=32, scaling_factor=0.18215):
+        super().__init__()
+        block_out_channels = tuple(int(c) for c in block_out_channels)
+        for c in block_out_channels:
+            if c % norm_num_groups:
+                raise WfaeError(f"AutoencoderKL: {c} channels are not divisible into {norm_num_groups} groups")
+        self.latent_channels, self.scaling_factor, self.sample_size = latent_channels, scaling_factor, sample_size
+        self.downscale = 2 ** (len(block_out_channels) - 1)
+        self.encoder = Encoder(in_channels=in_channels, out_channels=latent_channels,
+                               down_block_types=tuple(down_block_types), block_out_channels=block_out_channels,
+                               layers_per_block=layers_per_block, act_fn=act_fn, norm_num_groups=norm_num_groups,
+                               double_z=True)
+        self.decoder = Decoder(in_channels=latent_channels, out_channels=out_channels, up_block_types=tuple(up_block_types),
+                               block_out_channels=block_out_channels, layers_per_block=layers_per_block,
+                               norm_num_groups=norm_num_groups, act_fn=act_fn)
+        self.quant_conv = tnn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
+        self.post_quant_conv = tnn.Conv2d(latent_channels, latent_channels, 1)
+        self.use_slicing = False
+        self.eval()
+        for p in self.parameters():
+            p.requires_grad_(False)
+
+    def train(self, mode=True):
+        return super().train(False)   # frozen: there is no training-mode behaviour
+
+    @staticmethod
+    def _check(what, x, channels):
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != channels:
+            raise WfaeError(f"AutoencoderKL.{what}: expected (N, {channels}, H, W), got "
+                            f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise WfaeError(f"AutoencoderKL.{what} is forward only (frozen provider): call it under torch.no_grad() or "
+                            "detach the input")
+        return x.detach().contiguous()
+
+    @staticmethod
+    def _conv1x1(conv, x):
+        co, ci = conv.out_channels, conv.in_channels
+        return ops.conv1x1_fwd(x, conv.weight.detach().view(co, ci), conv.bias.detach())
+
+    @torch.no_grad()
+    def _encode(self, x):
+        d = self.downscale
+        if x.shape[2] % d or x.shape[3] % d:
+            raise WfaeError(f"AutoencoderKL.encode: the plane {tuple(x.shape[2:])} is not divisible by {d}")
+        return DiagonalGaussianDistribution(self._conv1x1(self.quant_conv, self.encoder(x)))
+
+    def encode(self, x):
+        return self._encode(self._check("encode", x, self.encoder.conv_in.in_channels))
+
+    @torch.no_grad()
+    def _decode(self, z):
+        return self.decoder(self._conv1x1(self.post_quant_conv, z))
+
+    def enable_slicing(self):
+        self.use_slicing = True
+
+    def disable_slicing(self):
+        self.use_slicing = False
+
+    def decode(self, z):
+        z = self._check("decode", z, self.latent_channels)
+        if self.use_slicing and z.shape[0] > 1:
+            return torch.cat([self._decode(s.contiguous()) for s in z.split(1)])
+        return self._decode(z)
+
+    def forward(self, sample, sample_posterior=False, return_posterior=False, generator=None):
+        posterior = self.encode(sample)
+        z = posterior.sample(generator=generator) if sample_posterior else posterior.mode()
+        dec = self.decode(z)
+        return (dec, posterior) if return_posterior else dec
