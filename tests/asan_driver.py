@@ -181,5 +181,48 @@ expect(lib.wfae_conv4x4s2_down(P, Q, R, 32, 256, 512, 96, 96, None), ANY_FAIL, "
 expect(lib.wfae_conv4x4s2_wgrad(P, Q, R, 32, 256, 512, 96, 96, 0, WS, big, None), ANY_FAIL, "conv4x4s2_wgrad")
 expect(lib.wfae_linear_fwd(P, Q, S, R, 32, 36864, 2048, WS, big, None), ANY_FAIL, "linear_fwd 36864->2048")
 expect(lib.wfae_linear_bwd_weight_splitk(P, Q, R, 2048, 512, 512, 0, WS, big, None), ANY_FAIL, "linear_bwd_weight_splitk")
+# scalar losses (csrc/loss.hip): one validation + workspace helper behind every forward entry point, one launcher behind
+# every gradient.  p stands for the first pointer (None for the null case); the workspace bound is blocks * 8 bytes with
+# the entry point's own block count: min(clamp((n / 16 + 255) / 256, 1, 4096), 1024) or min(ceil(n / 4096), 1024)
+def quarter_grid(n):
+    return min(max((n // 16 + 255) // 256, 1), 1024)
+
+
+def per_4096(n):
+    return min((n + 4095) // 4096, 1024)
+
+
+LOSS_FWD = {
+    "sigmoid_l1_fwd": (lambda p, n, wb: lib.wfae_sigmoid_l1_fwd(p, Q, R, S, 0.7, n, WS, wb, None), quarter_grid),
+    "l1_fwd": (lambda p, n, wb: lib.wfae_l1_fwd(p, Q, S, 0.7, n, WS, wb, None), quarter_grid),
+    "mean_fwd": (lambda p, n, wb: lib.wfae_mean_fwd(p, S, n, 0, 1.0, 0.7, WS, wb, None), quarter_grid),
+    "mean_fwd hinge": (lambda p, n, wb: lib.wfae_mean_fwd(p, S, n, 1, -1.0, 0.7, WS, wb, None), quarter_grid),
+    "sumsq": (lambda p, n, wb: lib.wfae_sumsq(p, n, S, WS, wb, None), quarter_grid),
+    "mse_fwd": (lambda p, n, wb: lib.wfae_mse_fwd(p, Q, S, n, WS, wb, None), per_4096),
+    "huber_fwd": (lambda p, n, wb: lib.wfae_huber_fwd(p, Q, S, n, 1.0, WS, wb, None), per_4096),
+}
+LOSS_BWD = {
+    "sigmoid_l1_bwd": lambda p, n: lib.wfae_sigmoid_l1_bwd(p, Q, S, 0.7, R, n, None),
+    "l1_bwd": lambda p, n: lib.wfae_l1_bwd(p, Q, S, 0.7, R, n, None),
+    "mean_bwd": lambda p, n: lib.wfae_mean_bwd(p, S, R, n, 0, 1.0, 0.7, None),
+    "mean_bwd hinge": lambda p, n: lib.wfae_mean_bwd(p, S, R, n, 1, -1.0, 0.7, None),
+    "mse_bwd": lambda p, n: lib.wfae_mse_bwd(p, Q, S, R, n, None),
+    "huber_bwd": lambda p, n: lib.wfae_huber_bwd(p, Q, S, R, n, 1.0, None),
+}
+for name, (fwd, blocks) in LOSS_FWD.items():
+    expect(fwd(None, 4097, big), NULL, f"{name} null")
+    expect(fwd(P, 0, big), SHAPE, f"{name} n = 0")
+    for n in (4097, 32 * 384 * 384):
+        expect(fwd(P, n, blocks(n) * 8 - 1), WSP, f"{name} workspace one byte short, n = {n}")
+        expect(fwd(P, n, blocks(n) * 8), ANY_FAIL - {WSP}, f"{name} exact workspace, n = {n}")
+    expect(fwd(P + 4, 1961, big), ANY_FAIL, f"{name} misaligned")
+for name, bwd in LOSS_BWD.items():
+    expect(bwd(None, 4097), NULL, f"{name} null")
+    expect(bwd(P, 0), SHAPE, f"{name} n = 0")
+    for n in (4097, 32 * 384 * 384):
+        expect(bwd(P, n), ANY_FAIL, f"{name} n = {n}")
+expect(lib.wfae_huber_fwd(P, Q, S, 4097, 0.0, WS, big, None), SHAPE, "huber_fwd delta = 0")
+expect(lib.wfae_huber_bwd(P, Q, S, R, 4097, -1.0, None), SHAPE, "huber_bwd delta < 0")
+expect(lib.wfae_huber_fwd(None, Q, S, 4097, 0.0, WS, big, None), NULL, "huber_fwd null before delta")
 assert lib.wfae_version() == 103 and lib.wfae_workspace_bytes(1 << 24) >= (1 << 26)
 print(f"asan driver: {checked} calls, no sanitizer report")

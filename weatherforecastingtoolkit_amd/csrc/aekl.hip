@@ -266,16 +266,6 @@ __global__ __launch_bounds__(256) void aekl_pack_kernel(const float* __restrict_
   }
 }
 
-// sum over the block, returned to every thread
-__device__ __forceinline__ double block_sum_bcast(double v, double* red, double* bc) {
-  const double r = block_sum(v, red);
-  if (threadIdx.x == 0) *bc = r;
-  __syncthreads();
-  const double out = *bc;
-  __syncthreads();
-  return out;
-}
-
 constexpr int kGnSlice = 16384;   // elements of a group one workgroup reduces
 
 // level 1: (mean, M2) of slice blockIdx.x of group blockIdx.y (a group of NCHW is one contiguous span of L floats)
@@ -288,14 +278,14 @@ __global__ __launch_bounds__(256) void aekl_gn_part_kernel(const float* __restri
   const float* __restrict__ xs = x + (long)blockIdx.y * L + b0;
   float s = 0.f;
   for (int i = threadIdx.x; i < cnt; i += 256) s += xs[i];
-  const double mu = block_sum_bcast((double)s, red, &bc) / (double)cnt;
+  const double mu = block_sum_all((double)s, red, &bc) / (double)cnt;
   const float muf = (float)mu;
   float q = 0.f;
   for (int i = threadIdx.x; i < cnt; i += 256) {
     const float d = xs[i] - muf;
     q = fmaf(d, d, q);
   }
-  const double m2 = block_sum_bcast((double)q, red, &bc);
+  const double m2 = block_sum_all((double)q, red, &bc);
   if (threadIdx.x == 0) {
     // M2 about the exact slice mean mu, from the sum about its fp32 rounding muf
     const double dm = (double)muf - mu;
@@ -389,7 +379,7 @@ __global__ __launch_bounds__(256) void aekl_softmax_kernel(const float* __restri
   mx = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
   float s = 0.f;
   for (int i = threadIdx.x; i < cols; i += 256) s += expf(xr[i] * scale - mx);
-  const float inv = (float)(1.0 / block_sum_bcast((double)s, red, &bc));
+  const float inv = (float)(1.0 / block_sum_all((double)s, red, &bc));
   for (int i = threadIdx.x; i < cols; i += 256) yr[i] = expf(xr[i] * scale - mx) * inv;
 }
 

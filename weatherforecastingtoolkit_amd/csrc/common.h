@@ -62,6 +62,15 @@ __device__ __forceinline__ double block_sum(double v, double* sm /* >= 16 double
   }
   return r;
 }
+// the same sum returned to every thread; bc: one LDS double for the broadcast
+__device__ __forceinline__ double block_sum_all(double v, double* red, double* bc) {
+  const double r = block_sum(v, red);
+  if (threadIdx.x == 0) *bc = r;
+  __syncthreads();
+  const double out = *bc;
+  __syncthreads();
+  return out;
+}
 
 // GELU(approximate='none') = u * Phi(u) and its derivative Phi(u) + u * phi(u).
 // Phi through a rational-exponential form of the upper tail,  1 - Phi(|u|) = t Q(t) exp(-u^2 / 2),  t = 1 / (1 + p |u|),
@@ -112,6 +121,17 @@ __device__ __forceinline__ float gelu_grad_f(float u) {
 __device__ __forceinline__ float sigmoid_f(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// blocks of 256 threads for a grid-stride loop over n elements, per_thread of them to a thread, at most 4096 blocks
+inline int grid_1d(long n, int per_thread = 4) {
+  long b = (n / per_thread + 255) / 256;
+  if (b > 4096) b = 4096;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+// out_f[0] (float) and / or out_d[0] (double) = mul * the sum of `parts` fp64 partials, by one block in a fixed order
+// (loss.hip: the second launch of every two-launch scalar reduction)
+int scalar_finalize(const double* part, long parts, double mul, float* out_f, double* out_d, hipStream_t st,
+                    const char* what);
 
 // x == h + m + l exactly, each a bf16 (round to nearest even; both residuals are exact fp32 differences): the operand form
 // of the split GEMMs (splitgemm.hip)

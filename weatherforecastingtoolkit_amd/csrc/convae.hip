@@ -1,5 +1,5 @@
 // convae.hip — kernels of the conv latent autoencoder (reference experiments/v1_experiments/pretrained_ae_convae_sevir/
-// train.py:58-143 `ConvEncoder`, `ConvDecoder`, `ConvModel`; :155 `nn.HuberLoss`).
+// train.py:58-143 `ConvEncoder`, `ConvDecoder`, `ConvModel`); its Huber loss is in loss.hip.
 //
 // The fused unit ("CLN"):  y = LeakyReLU_slope(LayerNorm_sample(conv(x) + bias) * gamma + beta)  for the three convolution
 // kinds of the model, all with padding 1:  kind 0 = Conv2d 3x3 stride 1, kind 1 = Conv2d 4x4 stride 2,
@@ -51,16 +51,6 @@ __device__ __forceinline__ bool tap_src(int d, int k, int lim, int& s) {
 template <bool T>
 __device__ __forceinline__ int w_index(int co, int ci, int tap, int Cin, int Cout, int KK) {
   return T ? (ci * Cout + co) * KK + tap : (co * Cin + ci) * KK + tap;
-}
-
-// sum over the block, returned to every thread; bc: one LDS double for the broadcast
-__device__ __forceinline__ double block_sum_all(double v, double* red, double* bc) {
-  const double r = block_sum(v, red);
-  if (threadIdx.x == 0) *bc = r;
-  __syncthreads();
-  const double out = *bc;
-  __syncthreads();
-  return out;
 }
 
 // LDS layout of both kernels: [16 + 2 doubles][u / du: E floats, padded to 4][weights, transposed to [tap][ci][co padded
@@ -331,38 +321,6 @@ __global__ __launch_bounds__(256) void wfae_cln_bwd_final_kernel(const float* __
   }
 }
 
-__device__ __forceinline__ double huber_term(float a, float b, float delta) {
-  const float d = a - b, ad = fabsf(d);
-  return ad <= delta ? 0.5 * (double)d * (double)d : (double)delta * ((double)ad - 0.5 * (double)delta);
-}
-
-__global__ __launch_bounds__(256) void wfae_huber_part_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                              double* __restrict__ part, long n, float delta) {
-  __shared__ double sm[16];
-  const long stride = (long)gridDim.x * blockDim.x;
-  double s = 0.0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) s += huber_term(a[i], b[i], delta);
-  const double r = block_sum(s, sm);
-  if (threadIdx.x == 0) part[blockIdx.x] = r;
-}
-
-__global__ void wfae_huber_finalize_kernel(const double* __restrict__ part, int n, double scale, float* __restrict__ out) {
-  __shared__ double sm[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) s += part[i];
-  const double r = block_sum(s, sm);
-  if (threadIdx.x == 0) out[0] = (float)(r * scale);
-}
-
-__global__ __launch_bounds__(256) void wfae_huber_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                             const float* __restrict__ g, float inv_n, float delta,
-                                                             float* __restrict__ da, long n) {
-  const float gv = g[0] * inv_n;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    da[i] = gv * fminf(fmaxf(a[i] - b[i], -delta), delta);
-}
-
 int cln_shape(const char* what, int kind, int N, int Cin, int Cout, int H, int W, float slope, ClnShape* s) {
   WFAE_REQUIRE(kind >= 0 && kind <= 2, WFAE_ERR_BAD_SHAPE,
                "%s: kind %d (0 = 3x3 s1, 1 = 4x4 s2, 2 = transposed 4x4 s2)", what, kind);
@@ -479,35 +437,6 @@ int wfae_cln_bwd(const float* dy, const float* xhat, const float* rstd, const fl
   hipLaunchKernelGGL(wfae_cln_bwd_final_kernel, dim3(cdiv((int64_t)E + nW + Cout, 256)), dim3(256), 0, st, dy, xhat,
                      gamma, beta, dwp, dbp, dgamma, dbeta, dw, dbias, N, E, nW, Cout, slope);
   return check_launch("cln_bwd_final");
-}
-
-int wfae_huber_fwd(const float* pred, const float* target, float* loss, int64_t n, float delta, void* ws,
-                   size_t ws_bytes, wfae_stream_t stream) {
-  WFAE_REQUIRE(pred && target && loss, WFAE_ERR_NULL_POINTER, "huber_fwd: null pointer");
-  WFAE_REQUIRE(n > 0, WFAE_ERR_BAD_SHAPE, "huber_fwd: bad size");
-  WFAE_REQUIRE(delta > 0.f, WFAE_ERR_BAD_SHAPE, "huber_fwd: delta must be positive (got %g)", (double)delta);
-  int blocks = cdiv(n, 256 * 16);
-  if (blocks > 1024) blocks = 1024;
-  WFAE_REQUIRE(ws && ws_bytes >= (size_t)blocks * sizeof(double), WFAE_ERR_WORKSPACE, "huber_fwd: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(wfae_huber_part_kernel, dim3(blocks), dim3(256), 0, st, pred, target, (double*)ws, (long)n, delta);
-  int rc = check_launch("huber_fwd");
-  if (rc) return rc;
-  hipLaunchKernelGGL(wfae_huber_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, blocks, 1.0 / (double)n,
-                     loss);
-  return check_launch("huber_finalize");
-}
-
-int wfae_huber_bwd(const float* pred, const float* target, const float* gloss, float* dpred, int64_t n, float delta,
-                   wfae_stream_t stream) {
-  WFAE_REQUIRE(pred && target && gloss && dpred, WFAE_ERR_NULL_POINTER, "huber_bwd: null pointer");
-  WFAE_REQUIRE(n > 0, WFAE_ERR_BAD_SHAPE, "huber_bwd: bad size");
-  WFAE_REQUIRE(delta > 0.f, WFAE_ERR_BAD_SHAPE, "huber_bwd: delta must be positive (got %g)", (double)delta);
-  int blocks = cdiv(n, 256 * 4);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(wfae_huber_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, target, gloss,
-                     (float)(1.0 / (double)n), delta, dpred, (long)n);
-  return check_launch("huber_bwd");
 }
 
 }  // extern "C"

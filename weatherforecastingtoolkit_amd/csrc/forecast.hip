@@ -1,7 +1,7 @@
 // forecast.hip — kernels of the Path-B latent linear forecaster (reference
 // experiments/v1_experiments/pretrained_ae_linear_sevir/train.py:67,73-83): difference the latent sequence
 // against the last input frame and lay it out as the (pixels x features) matrices of the per-latent-pixel
-// nn.Linear, the MSE loss, and the inverse layout (+ last frame) for decoding predictions.
+// nn.Linear, and the inverse layout (+ last frame) for decoding predictions.  The MSE loss is in loss.hip.
 #include "common.h"
 
 using namespace wfae;
@@ -57,34 +57,6 @@ __global__ __launch_bounds__(256) void unpack_add_kernel(const float* __restrict
   }
 }
 
-__global__ __launch_bounds__(256) void mse_part_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                       double* __restrict__ part, long n) {
-  __shared__ double sm[16];
-  const long stride = (long)gridDim.x * blockDim.x;
-  double s = 0.0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float d = a[i] - b[i];
-    s += (double)d * d;
-  }
-  const double r = block_sum(s, sm);
-  if (threadIdx.x == 0) part[blockIdx.x] = r;
-}
-
-__global__ void mse_finalize_kernel(const double* __restrict__ part, int n, double scale, float* __restrict__ out) {
-  __shared__ double sm[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) s += part[i];
-  const double r = block_sum(s, sm);
-  if (threadIdx.x == 0) out[0] = (float)(r * scale);
-}
-
-__global__ __launch_bounds__(256) void mse_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                      const float* __restrict__ g, float w, float* __restrict__ da, long n) {
-  const float gv = g[0] * w;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) da[i] = gv * (a[i] - b[i]);
-}
-
 }  // namespace
 
 extern "C" {
@@ -116,32 +88,6 @@ int wfae_latent_unpack_add(const float* pred, const float* v, float* out, int B,
   hipLaunchKernelGGL(unpack_add_kernel, dim3(cdiv(HW, 1 << PS), B), dim3(256), lds, (hipStream_t)stream, pred, v, out, T, Tin,
                      C, HW, PS);
   return check_launch("latent_unpack_add");
-}
-
-int wfae_mse_fwd(const float* pred, const float* target, float* loss, int64_t n, void* ws, size_t ws_bytes,
-                 wfae_stream_t stream) {
-  WFAE_REQUIRE(pred && target && loss, WFAE_ERR_NULL_POINTER, "mse_fwd: null pointer");
-  WFAE_REQUIRE(n > 0, WFAE_ERR_BAD_SHAPE, "mse_fwd: bad size");
-  int blocks = cdiv(n, 256 * 16);
-  if (blocks > 1024) blocks = 1024;
-  WFAE_REQUIRE(ws && ws_bytes >= (size_t)blocks * sizeof(double), WFAE_ERR_WORKSPACE, "mse_fwd: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mse_part_kernel, dim3(blocks), dim3(256), 0, st, pred, target, (double*)ws, (long)n);
-  int rc = check_launch("mse_fwd");
-  if (rc) return rc;
-  hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, blocks, 1.0 / (double)n, loss);
-  return check_launch("mse_finalize");
-}
-
-int wfae_mse_bwd(const float* pred, const float* target, const float* gloss, float* dpred, int64_t n,
-                 wfae_stream_t stream) {
-  WFAE_REQUIRE(pred && target && gloss && dpred, WFAE_ERR_NULL_POINTER, "mse_bwd: null pointer");
-  WFAE_REQUIRE(n > 0, WFAE_ERR_BAD_SHAPE, "mse_bwd: bad size");
-  int blocks = cdiv(n, 256 * 4);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(mse_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, target, gloss,
-                     (float)(2.0 / (double)n), dpred, (long)n);
-  return check_launch("mse_bwd");
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // norm_act.hip — bandwidth-bound kernels of the hot path: BatchNorm2d statistics
 // (wavefront-shuffle reductions, fp64 accumulation), fused BN-apply + exact GELU,
-// their backward, sigmoid + L1 loss, element-wise helpers and channel reductions.
+// their backward, element-wise helpers and channel reductions.
 // All kernels use 16-byte loads when HW % 4 == 0 (always true for the model).
 #include <stdlib.h>
 #include "common.h"
@@ -489,81 +489,6 @@ int launch_ew(const float* a, const float* b, float* out, int64_t n, hipStream_t
   return check_launch(what);
 }
 
-// ---------------------------------------------------------- sigmoid + L1
-// mode 0: recon = sigmoid(h), partial sum |recon - x| ; mode 1: h already is recon (plain L1)
-template <int MODE>
-__global__ __launch_bounds__(RT) void l1_fwd_kernel(const float* __restrict__ h, const float* __restrict__ x,
-                                                    float* __restrict__ recon, double* __restrict__ part, long n,
-                                                    int vec) {
-  __shared__ double sm[16];
-  const long stride = (long)gridDim.x * blockDim.x;
-  const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  double s = 0.0;
-  auto one = [&](float hv, float xv) {
-    const float r = MODE == 0 ? sigmoid_f(hv) : hv;
-    s += (double)fabsf(r - xv);
-    return r;
-  };
-  if (vec) {
-    const long n4 = n >> 2;
-    for (long i = i0; i < n4; i += stride) {
-      const float4 hv = reinterpret_cast<const float4*>(h)[i];
-      const float4 xv = reinterpret_cast<const float4*>(x)[i];
-      float4 r;
-      r.x = one(hv.x, xv.x); r.y = one(hv.y, xv.y); r.z = one(hv.z, xv.z); r.w = one(hv.w, xv.w);
-      if (MODE == 0) reinterpret_cast<float4*>(recon)[i] = r;
-    }
-    for (long i = (n4 << 2) + i0; i < n; i += stride) {
-      const float r = one(h[i], x[i]);
-      if (MODE == 0) recon[i] = r;
-    }
-  } else {
-    for (long i = i0; i < n; i += stride) {
-      const float r = one(h[i], x[i]);
-      if (MODE == 0) recon[i] = r;
-    }
-  }
-  const double r = block_sum(s, sm);
-  if (threadIdx.x == 0) part[blockIdx.x] = r;
-}
-
-__global__ void scalar_finalize_kernel(const double* __restrict__ part, int parts, double mul, float* out_f,
-                                       double* out_d) {
-  __shared__ double sm[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < parts; i += blockDim.x) s += part[i];
-  const double r = block_sum(s, sm);
-  if (threadIdx.x == 0) {
-    if (out_f) out_f[0] = (float)(r * mul);
-    if (out_d) out_d[0] = r * mul;
-  }
-}
-
-// mode 0: dh = g*w/n * sign(r-x) * r(1-r) ; mode 1: drecon = g*w/n * sign(r-x)
-template <int MODE>
-__global__ __launch_bounds__(256) void l1_bwd_kernel(const float* __restrict__ recon, const float* __restrict__ x,
-                                                     const float* __restrict__ gloss, float wn,
-                                                     float* __restrict__ dh, long n) {
-  const float g = gloss[0] * wn;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float r = recon[i];
-    const float d = r - x[i];
-    float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-    if (MODE == 0) sg *= r * (1.f - r);
-    dh[i] = g * sg;
-  }
-}
-
-__global__ __launch_bounds__(RT) void sumsq_kernel(const float* __restrict__ x, double* __restrict__ part, long n) {
-  __shared__ double sm[16];
-  const long stride = (long)gridDim.x * blockDim.x;
-  double s = 0.0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) s += (double)x[i] * x[i];
-  const double r = block_sum(s, sm);
-  if (threadIdx.x == 0) part[blockIdx.x] = r;
-}
-
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, long n, float lr,
                                                     float b1, float b2, float eps, float wd, float bc1,
@@ -643,29 +568,6 @@ __global__ __launch_bounds__(256) void pad2d_kernel(const float* __restrict__ sr
   }
 }
 
-// mode 0: sum x ; mode 1: sum relu(1 + sign*x)   (hinge terms, contperceptual.py:19-23)
-template <int MODE>
-__global__ __launch_bounds__(RT) void mean_part_kernel(const float* __restrict__ x, double* __restrict__ part, long n,
-                                                       float sign) {
-  __shared__ double sm[16];
-  const long stride = (long)gridDim.x * blockDim.x;
-  double s = 0.0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    s += MODE == 0 ? (double)x[i] : (double)fmaxf(1.f + sign * x[i], 0.f);
-  const double r = block_sum(s, sm);
-  if (threadIdx.x == 0) part[blockIdx.x] = r;
-}
-
-// mode 0: dx = g*w ; mode 1: dx = g*w*sign*[1 + sign*x > 0]
-template <int MODE>
-__global__ __launch_bounds__(256) void mean_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g, float w,
-                                                       float sign, float* __restrict__ dx, long n) {
-  const float gv = g[0] * w;
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    dx[i] = MODE == 0 ? gv : ((1.f + sign * x[i] > 0.f) ? gv * sign : 0.f);
-}
-
 __global__ __launch_bounds__(256) void scale_kernel(const float* __restrict__ x, const float* __restrict__ sdev, float s,
                                                     float* __restrict__ y, long n) {
   const float f = sdev ? sdev[0] * s : s;
@@ -726,13 +628,6 @@ __global__ __launch_bounds__(256) void convert_kernel(const void* __restrict__ s
       }
     }
   }
-}
-
-inline int grid_1d(long n, int per_thread = 4) {
-  long b = (n / per_thread + 255) / 256;
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 template <typename T>
@@ -1048,52 +943,6 @@ int wfae_reduce_sum(const float* x, int outer, int C, int inner, float* out, int
   return check_launch("reduce_sum_finalize");
 }
 
-static int l1_common(int mode, const float* h, const float* x, float* recon, float* loss, float weight,
-                     int64_t n, void* ws, size_t ws_bytes, hipStream_t st) {
-  WFAE_REQUIRE(h && x && loss && (mode == 1 || recon), WFAE_ERR_NULL_POINTER, "l1_fwd: null pointer");
-  WFAE_REQUIRE(n > 0, WFAE_ERR_BAD_SHAPE, "l1_fwd: bad size");
-  int blocks = grid_1d(n, 16);
-  if (blocks > 1024) blocks = 1024;
-  WFAE_REQUIRE(ws && ws_bytes >= (size_t)blocks * sizeof(double), WFAE_ERR_WORKSPACE, "l1_fwd: workspace too small");
-  const int vec = ((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(x) |
-                    reinterpret_cast<uintptr_t>(recon)) & 15) == 0;
-  if (mode == 0)
-    hipLaunchKernelGGL((l1_fwd_kernel<0>), dim3(blocks), dim3(RT), 0, st, h, x, recon, (double*)ws, (long)n, vec);
-  else
-    hipLaunchKernelGGL((l1_fwd_kernel<1>), dim3(blocks), dim3(RT), 0, st, h, x, recon, (double*)ws, (long)n, vec);
-  int rc = check_launch("l1_fwd");
-  if (rc) return rc;
-  hipLaunchKernelGGL(scalar_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, blocks,
-                     (double)weight / (double)n, loss, (double*)nullptr);
-  return check_launch("l1_finalize");
-}
-
-int wfae_sigmoid_l1_fwd(const float* h, const float* x, float* recon, float* loss, float weight, int64_t n,
-                        void* ws, size_t ws_bytes, wfae_stream_t stream) {
-  return l1_common(0, h, x, recon, loss, weight, n, ws, ws_bytes, (hipStream_t)stream);
-}
-int wfae_l1_fwd(const float* recon, const float* x, float* loss, float weight, int64_t n, void* ws,
-                size_t ws_bytes, wfae_stream_t stream) {
-  return l1_common(1, recon, x, nullptr, loss, weight, n, ws, ws_bytes, (hipStream_t)stream);
-}
-
-int wfae_sigmoid_l1_bwd(const float* recon, const float* x, const float* gloss, float weight, float* dh,
-                        int64_t n, wfae_stream_t stream) {
-  WFAE_REQUIRE(recon && x && gloss && dh, WFAE_ERR_NULL_POINTER, "sigmoid_l1_bwd: null pointer");
-  WFAE_REQUIRE(n > 0, WFAE_ERR_BAD_SHAPE, "sigmoid_l1_bwd: bad size");
-  hipLaunchKernelGGL((l1_bwd_kernel<0>), dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, recon, x, gloss,
-                     (float)((double)weight / (double)n), dh, (long)n);
-  return check_launch("sigmoid_l1_bwd");
-}
-int wfae_l1_bwd(const float* recon, const float* x, const float* gloss, float weight, float* drecon, int64_t n,
-                wfae_stream_t stream) {
-  WFAE_REQUIRE(recon && x && gloss && drecon, WFAE_ERR_NULL_POINTER, "l1_bwd: null pointer");
-  WFAE_REQUIRE(n > 0, WFAE_ERR_BAD_SHAPE, "l1_bwd: bad size");
-  hipLaunchKernelGGL((l1_bwd_kernel<1>), dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, recon, x, gloss,
-                     (float)((double)weight / (double)n), drecon, (long)n);
-  return check_launch("l1_bwd");
-}
-
 int wfae_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
                wfae_stream_t stream) {
@@ -1116,21 +965,6 @@ int wfae_adamw_c(float* p, const float* g, float* m, float* v, int64_t n, float 
                      beta2, one_minus_beta1, one_minus_beta2, eps, weight_decay, bias_corr1, sqrtf(bias_corr2),
                      grad_scale);
   return check_launch("adamw_c");
-}
-
-int wfae_sumsq(const float* x, int64_t n, double* out, void* ws, size_t ws_bytes, wfae_stream_t stream) {
-  WFAE_REQUIRE(x && out, WFAE_ERR_NULL_POINTER, "sumsq: null pointer");
-  WFAE_REQUIRE(n > 0, WFAE_ERR_BAD_SHAPE, "sumsq: bad size");
-  int blocks = grid_1d(n, 16);
-  if (blocks > 1024) blocks = 1024;
-  WFAE_REQUIRE(ws && ws_bytes >= (size_t)blocks * sizeof(double), WFAE_ERR_WORKSPACE, "sumsq: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(RT), 0, st, x, (double*)ws, (long)n);
-  int rc = check_launch("sumsq");
-  if (rc) return rc;
-  hipLaunchKernelGGL(scalar_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, blocks, 1.0,
-                     (float*)nullptr, out);
-  return check_launch("sumsq_finalize");
 }
 
 int wfae_vil_u8_to_f32(const uint8_t* src, float* dst, int NB, int H, int W, int T, float scale,
@@ -1160,37 +994,6 @@ int wfae_pad2d(const float* x, float* y, int64_t planes, int H, int W, int pad, 
   else
     hipLaunchKernelGGL((pad2d_kernel<0>), dim3(grid_1d(total, 1)), dim3(256), 0, (hipStream_t)stream, x, y, H, W, pad, total);
   return check_launch("pad2d");
-}
-
-int wfae_mean_fwd(const float* x, float* out, int64_t n, int hinge, float sign, float weight, void* ws, size_t ws_bytes,
-                  wfae_stream_t stream) {
-  WFAE_REQUIRE(x && out, WFAE_ERR_NULL_POINTER, "mean_fwd: null pointer");
-  WFAE_REQUIRE(n > 0, WFAE_ERR_BAD_SHAPE, "mean_fwd: bad size");
-  int blocks = grid_1d(n, 16);
-  if (blocks > 1024) blocks = 1024;
-  WFAE_REQUIRE(ws && ws_bytes >= (size_t)blocks * sizeof(double), WFAE_ERR_WORKSPACE, "mean_fwd: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  if (hinge)
-    hipLaunchKernelGGL((mean_part_kernel<1>), dim3(blocks), dim3(RT), 0, st, x, (double*)ws, (long)n, sign);
-  else
-    hipLaunchKernelGGL((mean_part_kernel<0>), dim3(blocks), dim3(RT), 0, st, x, (double*)ws, (long)n, sign);
-  int rc = check_launch("mean_fwd");
-  if (rc) return rc;
-  hipLaunchKernelGGL(scalar_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, blocks,
-                     (double)weight / (double)n, out, (double*)nullptr);
-  return check_launch("mean_finalize");
-}
-
-int wfae_mean_bwd(const float* x, const float* gout, float* dx, int64_t n, int hinge, float sign, float weight,
-                  wfae_stream_t stream) {
-  WFAE_REQUIRE(x && gout && dx, WFAE_ERR_NULL_POINTER, "mean_bwd: null pointer");
-  WFAE_REQUIRE(n > 0, WFAE_ERR_BAD_SHAPE, "mean_bwd: bad size");
-  const float w = (float)((double)weight / (double)n);
-  if (hinge)
-    hipLaunchKernelGGL((mean_bwd_kernel<1>), dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, x, gout, w, sign, dx, (long)n);
-  else
-    hipLaunchKernelGGL((mean_bwd_kernel<0>), dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, x, gout, w, sign, dx, (long)n);
-  return check_launch("mean_bwd");
 }
 
 int wfae_scale(const float* x, const float* scale_dev, float scale, float* y, int64_t n, wfae_stream_t stream) {

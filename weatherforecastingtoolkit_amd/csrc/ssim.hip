@@ -142,14 +142,6 @@ __global__ __launch_bounds__(256) void ssim_bwd_gather_kernel(const float* __res
   dy[q] = gout[0] * invN * (sa + 2.f * y[q] * sb + x[q] * sc);
 }
 
-__global__ void ssim_finalize_kernel(const double* __restrict__ part, long parts, double invN, float* out) {
-  __shared__ double sm[16];
-  double s = 0.0;
-  for (long i = threadIdx.x; i < parts; i += blockDim.x) s += part[i];
-  const double r = block_sum(s, sm);
-  if (threadIdx.x == 0) out[0] = (float)(r * invN);
-}
-
 // per image: sum (p-t)^2, min t, max t
 __global__ __launch_bounds__(256) void psnr_part_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                         int HW, int clamp, double* __restrict__ psum,
@@ -213,9 +205,7 @@ int wfae_ssim_fwd(const float* x, const float* y, float* out, int NB, int H, int
                      (double*)ws, (float*)nullptr);
   int rc = check_launch("ssim_fwd");
   if (rc) return rc;
-  hipLaunchKernelGGL(ssim_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, (long)NB * tiles,
-                     1.0 / ((double)NB * Ho * Wo), out);
-  return check_launch("ssim_finalize");
+  return scalar_finalize((const double*)ws, (long)NB * tiles, 1.0 / ((double)NB * Ho * Wo), out, nullptr, st, "ssim_finalize");
 }
 
 int wfae_ssim_bwd(const float* x, const float* y, const float* gout, float* dy, int NB, int H, int W, void* ws,
