@@ -567,6 +567,36 @@ int wfae_series_decomp_bwd(const float* dseasonal, const float* dtrend, float* d
 int wfae_dlinear_frames(const float* a, const float* v, float* out, int B, int R, int M, int L, int P, int cf, int mode,
                         wfae_stream_t stream);
 
+/* ---- intensity-statistics MLP forecaster (reference experiments/v1_experiments/prediff_mlp_sevir/train.py:20-38 `MLP`,
+ * :56-70 training_step).  Added within ABI version 103; nothing changed.
+ * seq_intensity_stats: seq is a batch of B sequences of T frames of HW pixels, fp32, in one of two memory orders:
+ *   t_innermost = 0: (B, T, HW), every frame contiguous — what the 'NHWT' loader view has underneath;
+ *   t_innermost != 0: (B, HW, T), the frame index fastest — a contiguous 'NHWT' tensor.
+ *   x (B, t_in) = the mean of each of the first t_in frames.  The other P = T - t_in frames, frame-major, are cut into
+ *   `groups` chunks of P HW / groups consecutive elements: target (B, 2 groups) = the chunk means, then the chunk
+ *   standard deviations (unbiased, n - 1).  P % groups must be 0 (a chunk is whole frames) else WFAE_ERR_BAD_SHAPE.
+ *   Every element is read once, with aligned 16-byte loads wherever a whole quad lies inside the piece a workgroup owns
+ *   (seq needs 4-byte alignment only; frames need not start on a 16-byte boundary).  The first launch leaves
+ *   (count, mean, M2) partials in ws — per 8192-element window of a frame (two passes over registers), or per frame and
+ *   workgroup in the (B, HW, T) order (shifted sums per lane, pooled by frame) — the second pools them in fp64 in a
+ *   fixed order, partials -> frames -> groups: n = sum n_k, mean = sum n_k mean_k / n, M2 = sum (M2_k + n_k (mean_k -
+ *   mean)^2), the K-way form of Chan's update.  E[x^2] - E[x]^2 is never formed.  No atomics: results are bitwise
+ *   repeatable.
+ *   ws >= seq_intensity_stats_ws_bytes.  T <= 256.
+ * mlp3_mse: pred (B, out) = W3 relu(W2 relu(W1 x + b1) + b2) + b3 for x (B, in), W1 (hidden, in), W2 (hidden, hidden),
+ *   W3 (out, hidden) (nn.Linear layout); loss[0] = mean((pred - target)^2) (fp64 sum, fixed order); dw1 .. db3 = the
+ *   gradients of loss with respect to the six parameters (overwritten) — all in ONE launch of one workgroup, fp32,
+ *   fixed summation order.  forward_only != 0: pred only (and loss when target and loss are both given); the gradient
+ *   pointers are ignored.  Served: in, out <= 32, hidden <= 256, B <= 64 (one workgroup carries the whole step), else
+ *   WFAE_ERR_UNSUPPORTED.  ws >= (4 B hidden + B out) floats (2 B hidden when forward_only). */
+size_t wfae_seq_intensity_stats_ws_bytes(int B, int T, int64_t HW, int t_innermost);
+int wfae_seq_intensity_stats(const float* seq, float* x, float* target, int B, int T, int64_t HW, int t_in, int groups,
+                             int t_innermost, void* ws, size_t ws_bytes, wfae_stream_t stream);
+int wfae_mlp3_mse(const float* x, const float* target, const float* w1, const float* b1, const float* w2,
+                  const float* b2, const float* w3, const float* b3, float* pred, float* loss, float* dw1, float* db1,
+                  float* dw2, float* db2, float* dw3, float* db3, int B, int in, int hidden, int out, int forward_only,
+                  void* ws, size_t ws_bytes, wfae_stream_t stream);
+
 /* ---- conv latent autoencoder (reference experiments/v1_experiments/pretrained_ae_convae_sevir/train.py:58-143
  * `ConvEncoder`, `ConvDecoder`, `ConvModel`; :155 `nn.HuberLoss`).
  * The fused unit ("CLN"): y (N, Cout, Ho, Wo) = LeakyReLU_slope(LN(conv(x) + bias) * gamma + beta), x (N, Cin, H, W).

@@ -1209,6 +1209,59 @@ def series_decomp(x, K):
     return SeriesDecompFn.apply(x, K)
 
 
+class Mlp3MseFn(Function):
+    """Linear-ReLU-Linear-ReLU-Linear + F.mse_loss of the intensity-statistics forecaster (reference
+    v1_experiments/prediff_mlp_sevir/train.py:20-38, :65-66) -> (loss, pred) from ONE launch (csrc/prediff.hip) that
+    also leaves the six parameter gradients of the loss; backward scales them by the upstream gradient into the
+    parameters' gradient buffers — one launch when the six buffers are consecutive in the gradient arena, else one
+    each.  x and target are data: they get no gradient, and asking for one is an error."""
+
+    @staticmethod
+    def forward(ctx, x, target, w1, b1, w2, b2, w3, b3):
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            raise ops._lib.WfaeError("mlp3_mse_loss: no gradient with respect to x or target is implemented")
+        params = (w1, b1, w2, b2, w3, b3)
+        sizes = [(p.numel() + 3) // 4 * 4 for p in params]   # the arena's 16-byte slots
+        # padding floats between slots travel into the arena with the one-launch scale: they must stay zero there
+        padded = any(n != p.numel() for p, n in zip(params[:-1], sizes[:-1]))
+        flat = (torch.zeros if padded else torch.empty)(sum(sizes), dtype=torch.float32, device=x.device)
+        grads, off = [], 0
+        for p, n in zip(params, sizes):
+            grads.append(flat[off:off + p.numel()].view_as(p))
+            off += n
+        pred, loss = ops.mlp3_mse(_c(x), _c(target), *params, grads=grads)
+        ctx.params, ctx.flat, ctx.grads = params, flat, grads
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, g, _gpred):
+        g = _c(g).view(1)
+        bufs = [grad_buffer(p) for p in ctx.params]
+        step = [(p.numel() + 3) // 4 * 4 * 4 for p in ctx.params]
+        if all(bufs[i + 1].data_ptr() == bufs[i].data_ptr() + step[i] for i in range(5)) and \
+                all(b._base is not None and b._base is bufs[0]._base for b in bufs):
+            # consecutive slots of one arena: the padding floats between them are scaled along (they are never read)
+            n = ctx.flat.numel() - (step[5] // 4 - ctx.params[5].numel())
+            dst = bufs[0]._base.as_strided((n,), (1,), bufs[0].storage_offset())
+            ops.scale(ctx.flat[:n], 1.0, g, out=dst)
+        else:
+            for src, dst in zip(ctx.grads, bufs):
+                ops.scale(src, 1.0, g, out=dst)
+        return (None, None, *bufs)
+
+
+def mlp3_mse_loss(x, target, w1, b1, w2, b2, w3, b3):
+    """-> (loss, pred)"""
+    return Mlp3MseFn.apply(x, target, w1, b1, w2, b2, w3, b3)
+
+
+def mlp3(x, w1, b1, w2, b2, w3, b3):
+    """forward only: pred (B, out), no graph"""
+    return ops.mlp3_mse(_c(x.detach()), None, w1.detach(), b1.detach(), w2.detach(), b2.detach(), w3.detach(),
+                        b3.detach())[0]
+
+
 class ConvLayerNormActFn(Function):
     """one unit of the conv latent autoencoder (reference v1_experiments/pretrained_ae_convae_sevir/train.py:62-108):
     LeakyReLU_slope(LayerNorm([C, H, W])(conv(x) + bias)) in one launch per sample batch (csrc/convae.hip); kind 0 =

@@ -1492,6 +1492,80 @@ def dlinear_forecast(pred, v, L, cf=1):
     return out
 
 
+# ---- intensity-statistics MLP forecaster (include/wfae.h "intensity-statistics MLP forecaster") ---------------------
+def _chk_dev_f32(*ts):
+    """_chk without the contiguity rule, for entry points that take the memory order as an argument"""
+    for t in ts:
+        if not t.is_cuda:
+            raise _lib.WfaeError("wfae kernels need device tensors (the HIP path has no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise _lib.WfaeError(f"wfae kernels are fp32, got {t.dtype}")
+
+
+def seq_intensity_stats(batch, t_in, groups=4):
+    """batch: 'NHWT' sequences (B, H, W, T) fp32 -> (x (B, t_in), target (B, 2 * groups)): the mean of each of the
+    first t_in frames; mean, then unbiased std, of `groups` equal runs of the remaining frames (reference
+    v1_experiments/prediff_mlp_sevir/train.py:56-64).  The batch is read once, in the memory order it has — the
+    frame-contiguous storage under the loader's permuted view, or a contiguous T-innermost tensor — never copied."""
+    _chk_dev_f32(batch)
+    if batch.dim() != 4:
+        raise _lib.WfaeError(f"seq_intensity_stats: expected an 'NHWT' batch (B, H, W, T), got {tuple(batch.shape)}")
+    b, h, w, t = batch.shape
+    if batch.is_contiguous():
+        t_innermost = 1
+    elif batch.permute(0, 3, 1, 2).is_contiguous():
+        t_innermost = 0
+    else:
+        raise _lib.WfaeError(f"seq_intensity_stats: strides {batch.stride()} of an 'NHWT' batch {tuple(batch.shape)} "
+                             "are neither T-innermost contiguous nor a permuted view of a contiguous (B, T, H, W) "
+                             "tensor; the kernel does not copy")
+    if not 0 < t_in < t or groups < 1 or (t - t_in) % groups:
+        raise _lib.WfaeError(f"seq_intensity_stats: pred_frames = {t - t_in} (of {t} frames, {t_in} input frames) must "
+                             f"be a positive multiple of groups = {groups}: a group is a run of whole frames")
+    x = torch.empty((b, t_in), dtype=torch.float32, device=batch.device)
+    target = torch.empty((b, 2 * groups), dtype=torch.float32, device=batch.device)
+    ws = workspace(_lib.load().wfae_seq_intensity_stats_ws_bytes(b, t, h * w, t_innermost))
+    _call("wfae_seq_intensity_stats", 0, 4 * batch.numel(), _p(batch), _p(x), _p(target), b, t, h * w, t_in, groups,
+          t_innermost, ws.data_ptr(), ws.numel(), _stream())
+    return x, target
+
+
+def _mlp3_dims(x, w1, b1, w2, b2, w3, b3):
+    if x.dim() != 2:
+        raise _lib.WfaeError(f"mlp3: expected x (B, in), got {tuple(x.shape)}")
+    b, i = x.shape
+    h, o = w1.shape[0], w3.shape[0]
+    want = [(h, i), (h,), (h, h), (h,), (o, h), (o,)]
+    got = [tuple(t.shape) for t in (w1, b1, w2, b2, w3, b3)]
+    if got != want:
+        raise _lib.WfaeError(f"mlp3: parameter shapes {got}, expected {want} for x {tuple(x.shape)}")
+    return b, i, h, o
+
+
+def mlp3_mse(x, target, w1, b1, w2, b2, w3, b3, grads=None):
+    """Linear-ReLU-Linear-ReLU-Linear + F.mse_loss in one launch -> (pred (B, out), loss).  grads: six tensors shaped
+    like the parameters, overwritten with d loss / d parameter; None: forward only.  target None (forward only):
+    pred alone, loss is None."""
+    _chk(x, target, w1, b1, w2, b2, w3, b3, *(grads or ()))
+    b, i, h, o = _mlp3_dims(x, w1, b1, w2, b2, w3, b3)
+    if target is not None and tuple(target.shape) != (b, o):
+        raise _lib.WfaeError(f"mlp3_mse: target shape {tuple(target.shape)}, expected {(b, o)}")
+    if grads is not None:
+        if target is None:
+            raise _lib.WfaeError("mlp3_mse: gradients need a target")
+        if [tuple(g.shape) for g in grads] != [tuple(p.shape) for p in (w1, b1, w2, b2, w3, b3)]:
+            raise _lib.WfaeError("mlp3_mse: gradient buffers must be shaped like the six parameters")
+    pred = torch.empty((b, o), dtype=torch.float32, device=x.device)
+    loss = None if target is None else torch.empty((), dtype=torch.float32, device=x.device)
+    ws = workspace(4 * (4 * b * h + b * o))
+    g = [_p(t) for t in grads] if grads is not None else [None] * 6
+    macs = b * (i * h + h * h + h * o)
+    _call("wfae_mlp3_mse", 2 * macs * (1 if grads is None else 3), 4 * (i * h + h * h + h * o) * (1 if grads is None else 2),
+          _p(x), _p(target), _p(w1), _p(b1), _p(w2), _p(b2), _p(w3), _p(b3), _p(pred), _p(loss), *g, b, i, h, o,
+          int(grads is None), ws.data_ptr(), ws.numel(), _stream())
+    return pred, loss
+
+
 # ---- conv latent autoencoder (include/wfae.h "conv latent autoencoder"): the fused conv + LayerNorm + LeakyReLU unit
 CLN_KINDS = {"conv3": 0, "down4": 1, "up4": 2}
 
