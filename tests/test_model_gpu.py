@@ -269,7 +269,10 @@ def test_tf_variant_golden(dev):
 
 
 def test_tf_dropout_and_optimizer_runs(dev):
-    """train mode with the reference's dropout 0.1 (own counter-based RNG) + AdamW skipping the unused template"""
+    """train mode with the reference's dropout 0.1 (own counter-based RNG) + AdamW skipping the unused template.
+    Only that the step runs: the masks, their scaling, the backward's use of the forward's mask and the seed stream are
+    checked numerically in tests/test_transformer_gpu.py (test_dropout_*, test_mha_fwd_bwd,
+    test_encoder_layer_train_mode_dropout, test_tf_model_seed_stream)."""
     from weatherforecastingtoolkit_amd import functional as Fn
     from weatherforecastingtoolkit_amd.optim import FusedAdamW
     from weatherforecastingtoolkit_amd.pipeline.models.ae_64x8x8_tf import PosAwareAE_TF

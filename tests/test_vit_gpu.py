@@ -75,7 +75,9 @@ def test_vit_train_step_golden(dev):
 
 
 def test_vit_pieces_vs_torch(dev):
-    """single-query attention, batch-first attention with head dim 64, patch (un)folding against torch"""
+    """single-query attention, batch-first attention with head dim 64, patch (un)folding against torch, one shape each;
+    the sweeps over ragged shapes, dropout, a bias in unpatchify and the row-copy helpers are in
+    tests/test_transformer_gpu.py (against the float64 restatement tests/transformer_ref.py)"""
     import torch.nn.functional as F
     from weatherforecastingtoolkit_amd import ops
     torch.manual_seed(0)

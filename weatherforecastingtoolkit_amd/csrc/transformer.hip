@@ -71,7 +71,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
       const float h = x[(long)r * E + i] + (res ? res[(long)r * E + i] : 0.f);
       const float xh = (h - mu) * rs;
       const float d = dy[(long)r * E + i];
-      dx[(long)r * E + i] = rs * (g[i] * d - s1 - xh * s2);
+      // the product rounded as the first pass rounded it into s1, not fused into the subtraction: fma(g, d, -s1) adds
+      // the product's rounding error times rstd (up to eps^-1/2 = 316) to rows whose gradient cancels exactly (E = 1)
+      const float gd = __fmul_rn(g[i], d);
+      dx[(long)r * E + i] = rs * (gd - s1 - xh * s2);
       pg[i] += d * xh;
       pb[i] += d;
     }
