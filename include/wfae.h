@@ -787,6 +787,20 @@ int wfae_sumsq(const float* x, int64_t n, double* out, void* ws, size_t ws_bytes
  * 1/255. */
 int wfae_vil_u8_to_f32(const uint8_t* src, float* dst, int NB, int H, int W, int T, float scale,
                        wfae_stream_t stream);
+/* The same conversion with the train-time augmentation of the reference's second loader fused in
+ * (pipeline/datasets/sevir/sevir.py:1035-1058: h-flip, v-flip, then torchvision's rotate with its defaults: nearest
+ * neighbour, no expand, centre of the image, zero fill), one transform per sample applied to all T frames.
+ * xf is a device fp32 (NB,4): cos(theta), sin(theta), hflip (0/1), vflip (0/1); theta counter-clockwise.  For output
+ * pixel (i, j), in fp32:
+ *   x_o = j + 0.5 - W/2,  y_o = i + 0.5 - H/2
+ *   xs = rintf(cos * x_o - sin * y_o + W/2 - 0.5),  ys = rintf(sin * x_o + cos * y_o + H/2 - 0.5)   (half to even)
+ *   dst[n][t][i][j] = scale * (0.f + 0.f)                                          if (ys, xs) is outside the image
+ *                   = scale * ((float)src[n][vflip ? H-1-ys : ys][hflip ? W-1-xs : xs][t] + 0.f)     otherwise
+ * The bounds test is made on the rounded integers, before the flips.  With the row (1, 0, 0, 0) the result is
+ * bit-identical to wfae_vil_u8_to_f32; with cos, sin in {0, +1, -1} on square frames it is torch.rot90.  Any H, W, T
+ * (16-byte stores where W % 4 == 0, dword stores otherwise). */
+int wfae_vil_augment_u8_to_f32(const uint8_t* src, const float* xf, float* dst, int NB, int H, int W, int T, float scale,
+                               wfae_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -2022,3 +2022,19 @@ def vil_u8_to_f32(src_nhwt, scale=1.0 / 255.0):
     dst = torch.empty((n, t, h, w), dtype=torch.float32, device=src_nhwt.device)
     _call("wfae_vil_u8_to_f32", 0, 5 * dst.numel(), src_nhwt.data_ptr(), _p(dst), n, h, w, t, scale, _stream())
     return dst
+
+
+def vil_augment_u8_to_f32(src_nhwt, xf, scale=1.0 / 255.0):
+    """uint8 (N,H,W,T) -> fp32 (N,T,H,W) * scale with one flip + nearest-neighbour rotation per sample in the same
+    pass; xf: fp32 (N,4) device rows (cos, sin, hflip, vflip) — include/wfae.h states the formula."""
+    if src_nhwt.dtype != torch.uint8 or not src_nhwt.is_cuda or not src_nhwt.is_contiguous() or src_nhwt.dim() != 4:
+        raise _lib.WfaeError("vil_augment_u8_to_f32 needs a contiguous uint8 (N,H,W,T) device tensor")
+    n, h, w, t = src_nhwt.shape
+    if (xf.dtype != torch.float32 or not xf.is_contiguous() or tuple(xf.shape) != (n, 4)
+            or xf.device != src_nhwt.device):
+        raise _lib.WfaeError(f"vil_augment_u8_to_f32 needs contiguous fp32 transform rows of shape ({n}, 4) on "
+                             f"{src_nhwt.device}")
+    dst = torch.empty((n, t, h, w), dtype=torch.float32, device=src_nhwt.device)
+    _call("wfae_vil_augment_u8_to_f32", 0, 5 * dst.numel(), src_nhwt.data_ptr(), xf.data_ptr(), _p(dst), n, h, w, t,
+          scale, _stream())
+    return dst

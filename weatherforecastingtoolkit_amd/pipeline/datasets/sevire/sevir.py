@@ -15,9 +15,14 @@ Events come either from memory (synthetic `synth.blob_events`, or any uint8 arra
 (`catalog.CatalogEventStore`: filtered SEVIR catalog + .npy / HDF5 files).
 `prefetch()` overlaps the host gather and the uint8 H2D copy of batch i+1 (pinned staging buffers, a copy
 stream) with the training step of batch i.  AWS download of the reference is out of scope.
+
+Train-time augmentation (`aug_mode`, the reference's SECOND loader, pipeline/datasets/sevir/sevir.py:1035-1058): one
+h-flip / v-flip / rotation per sequence, drawn on the host by `augment_params` and applied on the device inside the
+conversion kernel (`ops.vil_augment_u8_to_f32`), so the batch still crosses the bus as uint8 and is written once.
 """
 from __future__ import annotations
 
+import math
 import queue
 import threading
 
@@ -55,11 +60,73 @@ def change_layout_torch(data, in_layout="NHWT", out_layout="NHWT", ret_contiguou
     return data.contiguous() if ret_contiguous else data
 
 
+AUG_MODES = ("0", "1", "2")
+FIX_ROTATION_ANGLES = (0, 90, 180, 270)      # reference sevir/sevir.py:1047
+_M64 = (1 << 64) - 1
+
+
+def _mix64(x):
+    """splitmix64 finaliser: one well-mixed 64-bit word from another"""
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def augment_params(mode, seed, epoch, sequence_index):
+    """(hflip, vflip, angle_degrees) of ONE sequence for aug_mode `mode` ("1": angle ~ U(-180, 180); "2": angle from
+    {0, 90, 180, 270}; reference sevir/sevir.py:1037-1048).
+
+    A pure function of its arguments: the draws come from a torch.Generator seeded from (seed, epoch, global sequence
+    index) and nothing else, so the transform of a sequence does not depend on batch size, shard count, rank, prefetch
+    depth or the order of calls.  The draws are made the way the reference's transforms make them — `torch.rand(1) <
+    0.5` for each flip (RandomHorizontalFlip / RandomVerticalFlip), `uniform_(-180, 180)` for RandomRotation, a uniform
+    choice among the four angles for TransformsFixRotation.  Bit parity of the random STREAM with the reference is
+    neither possible nor a goal: there the numbers come from the global generators of whichever DataLoader worker
+    happens to serve the sample."""
+    mode = str(mode)
+    if mode not in AUG_MODES:
+        raise NotImplementedError(f"aug_mode {mode!r}: the reference knows {AUG_MODES}")
+    if mode == "0":
+        return (False, False, 0.0)
+    g = torch.Generator()
+    g.manual_seed(_mix64(_mix64(_mix64(int(seed) & _M64) ^ (int(epoch) & _M64)) ^ (int(sequence_index) & _M64)))
+    hflip = bool(torch.rand(1, generator=g) < 0.5)
+    vflip = bool(torch.rand(1, generator=g) < 0.5)
+    if mode == "1":
+        angle = float(torch.empty(1).uniform_(-180.0, 180.0, generator=g).item())
+    else:
+        angle = float(FIX_ROTATION_ANGLES[int(torch.randint(len(FIX_ROTATION_ANGLES), (1,), generator=g))])
+    return (hflip, vflip, angle)
+
+
+_QUARTER_TURNS = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))
+
+
+def transform_rows(params):
+    """[(hflip, vflip, angle_degrees)] -> fp32 (B, 4) rows (cos, sin, hflip, vflip) of ops.vil_augment_u8_to_f32.
+    cos and sin are taken in Python double and rounded to fp32 once, as torchvision builds its matrix; whole multiples
+    of 90 degrees (all of mode "2") get the exact 0 / +-1, so that a square frame comes out as torch.rot90 of itself."""
+    rows = torch.empty((len(params), 4), dtype=torch.float32)
+    for i, (hflip, vflip, angle) in enumerate(params):
+        q = angle / 90.0
+        if q == int(q):
+            c, s = _QUARTER_TURNS[int(q) % 4]
+        else:
+            th = math.radians(angle)
+            c, s = math.cos(th), math.sin(th)
+        rows[i, 0], rows[i, 1], rows[i, 2], rows[i, 3] = c, s, float(bool(hflip)), float(bool(vflip))
+    return rows
+
+
 class SEVIRFrameLoader:
     def __init__(self, events_u8, batch_size, seq_len=1, stride=1, layout="NTHW", shuffle=False,
-                 shuffle_seed=1, device=None, num_shard=1, rank=0):
+                 shuffle_seed=1, device=None, num_shard=1, rank=0, aug_mode="0", aug_seed=0):
         if layout not in LAYOUTS:
             raise NotImplementedError(f"layout {layout!r}: the reference's change_layout_torch knows {sorted(LAYOUTS)}")
+        if str(aug_mode) not in AUG_MODES:
+            raise NotImplementedError(f"aug_mode {aug_mode!r}: the reference knows {AUG_MODES}")
+        self.aug_mode, self.aug_seed, self.epoch = str(aug_mode), int(aug_seed), 0
         self.layout = layout
         if hasattr(events_u8, "read") and hasattr(events_u8, "event_shape"):
             # an event store (catalog + files): events are read on demand; shuffling is the catalog's job
@@ -103,6 +170,38 @@ class SEVIRFrameLoader:
                 seq_idx = 0
         return out
 
+    def set_epoch(self, epoch):
+        """the epoch the augmentation draws are keyed on; a running prefetch() keeps the epoch it started with"""
+        self.epoch = int(epoch)
+
+    def sequence_ids(self, index):
+        """global sequence indices (event * num_seq_per_event + seq) of this rank's batch `index`"""
+        n = self.num_seq_per_event
+        return [e * n + s for e, s in self.sample_indices(index * self.num_shard + self.rank)]
+
+    def batch_augment_params(self, index, epoch=None):
+        """[(hflip, vflip, angle)] of this rank's batch `index`"""
+        epoch = self.epoch if epoch is None else epoch
+        return [augment_params(self.aug_mode, self.aug_seed, epoch, i) for i in self.sequence_ids(index)]
+
+    def batch_transform_rows(self, index, epoch=None):
+        """host fp32 (B, 4) rows of this rank's batch `index`; None with aug_mode "0", which builds no rows and runs the
+        plain conversion kernel"""
+        if self.aug_mode == "0":
+            return None
+        return transform_rows(self.batch_augment_params(index, epoch))
+
+    def _convert(self, u8_dev, rows_dev):
+        """device uint8 'NHWT' batch (+ transform rows unless aug_mode is "0") -> the batch the loader yields"""
+        if rows_dev is None:
+            x = ops.vil_u8_to_f32(u8_dev, PREPROCESS_SCALE_01["vil"])
+        else:
+            x = ops.vil_augment_u8_to_f32(u8_dev, rows_dev, PREPROCESS_SCALE_01["vil"])
+        return self._wrap(LAYOUTS[self.layout](x))
+
+    def _wrap(self, x):
+        return {"vil": x}
+
     def batch_u8(self, index):
         """uint8 (B, H, W, seq_len) host batch, before preprocessing."""
         idx = self.sample_indices(index * self.num_shard + self.rank)
@@ -132,7 +231,8 @@ class SEVIRFrameLoader:
         if self.device is None or self.device.type != "cuda":
             raise RuntimeError("SEVIRFrameLoader preprocesses on the GPU: pass device='cuda:N'")
         u8 = u8.to(self.device, non_blocking=True)
-        return {"vil": LAYOUTS[self.layout](ops.vil_u8_to_f32(u8, PREPROCESS_SCALE_01["vil"]))}
+        rows = self.batch_transform_rows(index)
+        return self._convert(u8, None if rows is None else rows.to(self.device, non_blocking=True))
 
     def __iter__(self):
         for i in range(len(self)):
@@ -142,7 +242,9 @@ class SEVIRFrameLoader:
 class _Prefetcher:
     """Background thread: gather batch i+1 into a pinned uint8 buffer and start its H2D copy on a side stream while
     the consumer trains on batch i; the u8 -> fp32/255 + layout kernel runs on the consumer's stream after an event
-    wait.  `depth` pinned buffers / device buffers are recycled."""
+    wait.  `depth` pinned buffers / device buffers are recycled.  With augmentation on, the (B, 4) transform rows of a
+    batch travel with it: their own pinned buffer, a copy on the same stream in front of the same event.  A batch may be
+    shorter than the first one (the last batch of a loader that keeps its remainder): it uses the head of its slot."""
 
     def __init__(self, loader, depth=2, start=0):
         if loader.device is None or loader.device.type != "cuda":
@@ -158,6 +260,10 @@ class _Prefetcher:
         shape = ld.batch_u8(0).shape
         pinned = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(self.depth + 1)]
         dbuf = [torch.empty(shape, dtype=torch.uint8, device=dev) for _ in range(self.depth + 1)]
+        aug, epoch = ld.aug_mode != "0", ld.epoch
+        if aug:
+            pinned_xf = [torch.empty((shape[0], 4), dtype=torch.float32).pin_memory() for _ in range(self.depth + 1)]
+            dbuf_xf = [torch.empty((shape[0], 4), dtype=torch.float32, device=dev) for _ in range(self.depth + 1)]
         free_slots = queue.Queue()
         for i in range(self.depth + 1):
             free_slots.put(i)
@@ -172,27 +278,33 @@ class _Prefetcher:
                     if stop.is_set():
                         return
                     slot = free_slots.get()
-                    pinned[slot].numpy()[...] = ld.batch_u8(i)
+                    u8 = ld.batch_u8(i)
+                    b = u8.shape[0]
+                    pinned[slot].numpy()[:b] = u8
+                    if aug:
+                        pinned_xf[slot][:b] = ld.batch_transform_rows(i, epoch)
                     with torch.cuda.stream(copy_stream):
-                        dbuf[slot].copy_(pinned[slot], non_blocking=True)
+                        dbuf[slot][:b].copy_(pinned[slot][:b], non_blocking=True)
+                        if aug:
+                            dbuf_xf[slot][:b].copy_(pinned_xf[slot][:b], non_blocking=True)
                         ev = torch.cuda.Event()
                         ev.record(copy_stream)
-                    ready.put((slot, ev, None))
-                ready.put((None, None, None))
+                    ready.put((slot, b, ev, None))
+                ready.put((None, 0, None, None))
             except BaseException as e:      # surface loader errors in the consumer
-                ready.put((None, None, e))
+                ready.put((None, 0, None, e))
 
         th = threading.Thread(target=producer, daemon=True)
         th.start()
         try:
             while True:
-                slot, ev, err = ready.get()
+                slot, b, ev, err = ready.get()
                 if err is not None:
                     raise err
                 if slot is None:
                     break
                 torch.cuda.current_stream(dev).wait_event(ev)
-                out = {"vil": LAYOUTS[self.loader.layout](ops.vil_u8_to_f32(dbuf[slot], PREPROCESS_SCALE_01["vil"]))}
+                out = ld._convert(dbuf[slot][:b], dbuf_xf[slot][:b] if aug else None)
                 done = torch.cuda.Event()
                 done.record(torch.cuda.current_stream(dev))
                 yield out
