@@ -802,6 +802,29 @@ int wfae_vil_u8_to_f32(const uint8_t* src, float* dst, int NB, int H, int W, int
 int wfae_vil_augment_u8_to_f32(const uint8_t* src, const float* xf, float* dst, int NB, int H, int W, int T, float scale,
                                wfae_stream_t stream);
 
+/* The same conversion with a frame stride and block pooling fused in: what turns raw SEVIR (384 x 384 x 49) into
+ * sevir_lr (128 x 128 x 25) at factors (2, 3, 3).  src uint8 (NB,H,W,T) 'NHWT'; dst fp32 (NB,To,Ho,Wo) 'NTHW' with
+ * To = ceil(T / ft); output frame t' is raw frame t' * ft.
+ *   mode 0 (max): the reference's offline recipe (pipeline/datasets/sevire/sevir.py:575-616, [..., ::ft] then
+ *     block_reduce(block_size=(1, fh, fw, 1), func=np.max)).  Ho = ceil(H / fh), Wo = ceil(W / fw); a block that sticks
+ *     out of the image is reduced over its pixels inside (block_reduce pads with 0: the same for a max over uint8).
+ *   mode 1 (mean): the reference's runtime downsample_data_dict (:849-890, [::ft] then avg_pool2d(kernel_size=(fh, fw))).
+ *     Ho = H / fh, Wo = W / fw (floor): the remainder is dropped, as avg_pool2d drops it.
+ * Arithmetic, fp32, every operation rounded on its own (no fma, no reciprocal):
+ *   v(b)  = scale * ((float)b + offset)                        one add, then one multiply
+ *   max:  out = v(max of the block's bytes)
+ *   mean: acc = 0.f; for a in [0, fh): for b in [0, fw): acc = acc + v(byte[a][b]);  out = acc / (float)(fh * fw)
+ *     (bit-identical to torch.nn.functional.avg_pool2d of scale * (u8.float() + offset) on the CPU)
+ * Geometry: xf == NULL: output pixel (i, j) reduces block (i, j).  Otherwise xf is the device fp32 (NB,4) of
+ * wfae_vil_augment_u8_to_f32, applied on the POOLED grid Ho x Wo: the source pixel of its formula names the block to
+ * reduce, and a pixel whose rotated centre falls outside is exactly 0.f, whatever the offset (the reference rotates after
+ * preprocessing and fills with 0).  With ft = fh = fw = 1 and offset = 0 both modes are bit-identical to
+ * wfae_vil_u8_to_f32 (xf == NULL) and to wfae_vil_augment_u8_to_f32 (with rows).
+ * Errors, all before any launch: null src / dst; NB, H, W, T, ft, fh or fw < 1, H * W > INT_MAX, or mean with fh > H or
+ * fw > W (WFAE_ERR_BAD_SHAPE); mode not 0 or 1 (WFAE_ERR_UNSUPPORTED).  Any alignment of src and dst rows. */
+int wfae_vil_pool_u8_to_f32(const uint8_t* src, const float* xf /* may be NULL */, float* dst, int NB, int H, int W, int T,
+                            int ft, int fh, int fw, int mode, float scale, float offset, wfae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,20 +12,6 @@
 
 namespace wfae {
 
-// source offset (in pixels) of output pixel (i, j), or -1 where the rotated centre falls outside the image
-__device__ __forceinline__ int aug_src_pixel(int i, int j, int H, int W, float c, float s, bool hflip, bool vflip) {
-  const float cx = 0.5f * (float)W - 0.5f, cy = 0.5f * (float)H - 0.5f;
-  const float xo = (float)j - cx, yo = (float)i - cy;       // j + 0.5 - W/2, exact
-  const float xr = rintf(c * xo - s * yo + cx);
-  const float yr = rintf(s * xo + c * yo + cy);
-  // on the rounded values, before the flips; as floats, so that a NaN or a huge coordinate is outside, never an index
-  if (!(xr >= 0.f && xr <= (float)(W - 1) && yr >= 0.f && yr <= (float)(H - 1))) return -1;
-  int xs = (int)xr, ys = (int)yr;
-  if (hflip) xs = W - 1 - xs;
-  if (vflip) ys = H - 1 - ys;
-  return ys * W + xs;
-}
-
 // VEC = 4: a thread owns pixels (i, 4q .. 4q+3) (W % 4 == 0, dst 16-byte aligned); VEC = 1: one pixel
 template <int VEC>
 __global__ __launch_bounds__(256) void vil_augment_kernel(const uint8_t* __restrict__ src, const float* __restrict__ xf,

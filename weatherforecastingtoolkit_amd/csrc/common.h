@@ -212,6 +212,21 @@ __device__ __forceinline__ void st4(bf16_t* p, float4 v) {
   *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16(v.x, v.y), pack_bf16(v.z, v.w));
 }
 
+// loader geometry (augment.hip, vil_pool.hip): one flip + nearest-neighbour rotation per sample, include/wfae.h states it
+// source offset (in pixels) of output pixel (i, j), or -1 where the rotated centre falls outside the image
+__device__ __forceinline__ int aug_src_pixel(int i, int j, int H, int W, float c, float s, bool hflip, bool vflip) {
+  const float cx = 0.5f * (float)W - 0.5f, cy = 0.5f * (float)H - 0.5f;
+  const float xo = (float)j - cx, yo = (float)i - cy;       // j + 0.5 - W/2, exact
+  const float xr = rintf(c * xo - s * yo + cx);
+  const float yr = rintf(s * xo + c * yo + cy);
+  // on the rounded values, before the flips; as floats, so that a NaN or a huge coordinate is outside, never an index
+  if (!(xr >= 0.f && xr <= (float)(W - 1) && yr >= 0.f && yr <= (float)(H - 1))) return -1;
+  int xs = (int)xr, ys = (int)yr;
+  if (hflip) xs = W - 1 - xs;
+  if (vflip) ys = H - 1 - ys;
+  return ys * W + xs;
+}
+
 // Conv2d(C, 1, 3, padding=1): the decoder's full-resolution output convolution (c1conv.hip)
 int c1_wgrad_mfma(int flip, const float* big, const float* small, float* dw, int NB, int C, int H, int W, int accumulate,
                   void* ws, size_t ws_bytes, hipStream_t st);   // dconv.hip: weight gradients with one channel count = 1

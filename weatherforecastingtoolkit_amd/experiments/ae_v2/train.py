@@ -29,7 +29,7 @@ from ... import ops
 from ... import parallel, synth
 from ...nn import flush_bn_counters
 from ...pipeline import helpers
-from ...pipeline.datasets.sevire.sevir import SEVIRFrameLoader
+from ...pipeline.datasets.sevire.sevir import SEVIRFrameLoader, parse_presample, presample_line, resolve_presample
 from ...pipeline.models import ae_64x8x8_lin, ae_64x8x8_tf
 from .._gan import GanLoss, frozen
 
@@ -248,6 +248,9 @@ def main(argv=None):
                          "storage in HBM (the counterpart of bf16 autocast); WFAE_BF16_STORAGE=0 keeps the tensors fp32")
     ap.add_argument("--data-dir", default=None, help="SEVIR root (CATALOG.csv + data/); default: synthetic events")
     ap.add_argument("--data-format", choices=("npy", "h5"), default="npy")
+    ap.add_argument("--presample", type=parse_presample, default="auto", metavar="auto|none|T,H,W",
+                    help="with --data-dir: pool the events on the device as the loader converts them.  auto = (2, 3, 3) "
+                         "when the config names sevir_lr and the store holds raw 384x384x49 events, else none")
     ap.add_argument("--model", choices=("tf", "lin"), default="tf",
                     help="tf = ae_64x8x8_tf (what the reference ae_v2/train.py:18 imports), lin = ae_64x8x8_lin (ae_v2_2)")
     ap.add_argument("--test", action="store_true", help="run the test loop after training (trainer.test)")
@@ -265,6 +268,7 @@ def main(argv=None):
     size, frames = (384, 49) if cfg.dataset.name == "sevir" else (128, 25)
     B = cfg.dataset.batch_size
     nspe = 1 + (frames - cfg.dataset.seq_len) // cfg.dataset.stride
+    presample = None
     if args.data_dir:
         # real data: <data_dir>/CATALOG.csv + the event files (.npy, or .h5 when h5py is available), split by date
         # like the reference (train < 2019-01-01 <= val < 2019-06-01 <= test, sevire/sevir.py:1227-1243)
@@ -282,7 +286,10 @@ def main(argv=None):
         ev_test = store(start_date=d_test) if args.test else None     # opened only when the test loop will run
         if ev_train is None:
             raise ValueError(f"{cat_path}: no training events before {d_val:%Y-%m-%d}")
-        size = ev_train.event_shape[0]
+        presample, pooled = resolve_presample(args.presample, cfg.dataset.name, ev_train.event_shape)
+        size = pooled[0]
+        if presample is not None and rank == 0:
+            print(presample_line(presample, ev_train.event_shape, pooled), flush=True)
     else:
         n_events = max(2, (B * 8 * world) // nspe + 1)
         ev_train = synth.blob_events(n_events, size, frames, seed=1234)
@@ -293,7 +300,7 @@ def main(argv=None):
         if ev is None:
             return ()
         return SEVIRFrameLoader(ev, B, cfg.dataset.seq_len, cfg.dataset.stride, "NTHW", shuffle=shuffle, device=dev,
-                                num_shard=world, rank=rank)
+                                num_shard=world, rank=rank, presample=presample)
     loader, val_loader, test_loader = mk(ev_train, True), mk(ev_val, False), mk(ev_test, False)
     accum = cfg.trainer.accumulate_grad_batches
     total_steps = max(1, int(len(loader) * cfg.trainer.max_epochs / accum))  # reference :306

@@ -7,8 +7,9 @@ ret_contiguous False, as the reference builds it (:243-253).  A batch is a bare 
 
 What differs from train.py is the data path only: single sequences split into train / val by random_split, a fresh
 train permutation per epoch, and the flips + rotation of `aug_mode` applied inside the uint8 -> fp32 conversion kernel.
-Without --data-dir the events are synthetic (`synth.blob_events`).  Checkpoints are written like train.py's; resuming
-is train.py's feature and not repeated here.
+Without --data-dir the events are synthetic (`synth.blob_events`); with it, --presample (default auto) pools raw
+384 x 384 x 49 events to the 128 x 128 x 25 of the `sevirlr` config on the device.  Checkpoints are written like
+train.py's; resuming is train.py's feature and not repeated here.
 """
 from __future__ import annotations
 
@@ -27,6 +28,7 @@ from ... import parallel, synth
 from ...nn import flush_bn_counters
 from ...pipeline import helpers
 from ...pipeline.datasets.sevir.sevir import SEVIRLightningDataModule
+from ...pipeline.datasets.sevire.sevir import parse_presample, presample_line, resolve_presample
 from .train import CARRIED_KEYS, HERE, Model
 
 
@@ -37,6 +39,9 @@ def main(argv=None):
     ap.add_argument("--matmul-precision", default="high", choices=["highest", "high", "medium"])
     ap.add_argument("--data-dir", default=None, help="SEVIR root (CATALOG.csv + data/); default: synthetic events")
     ap.add_argument("--data-format", choices=("npy", "h5"), default="npy")
+    ap.add_argument("--presample", type=parse_presample, default="auto", metavar="auto|none|T,H,W",
+                    help="with --data-dir: pool the events on the device as the loader converts them.  auto = (2, 3, 3) "
+                         "when the config names sevirlr and the store holds raw 384x384x49 events, else none")
     args, unknown = ap.parse_known_args(argv)
     cfg = C.load(args.config, CARRIED_KEYS)
     cli = C.from_dotlist(unknown)
@@ -50,6 +55,7 @@ def main(argv=None):
 
     size, frames = (384, 49) if cfg.dataset.name == "sevir" else (128, 25)
     B = cfg.dataset.batch_size
+    presample = None
     if args.data_dir:
         # train + val before the reference's train_test_split_date, test after it (sevir/sevir.py:1087, 1175, 1197)
         import datetime
@@ -63,7 +69,10 @@ def main(argv=None):
             raise ValueError(f"{cat_path}: no events before {split:%Y-%m-%d}")
         ev_train = CatalogEventStore(cat_train, source)
         ev_test = CatalogEventStore(cat_test, source) if len(cat_test) else None
-        size = ev_train.event_shape[0]
+        presample, pooled = resolve_presample(args.presample, cfg.dataset.name, ev_train.event_shape)
+        size = pooled[0]
+        if presample is not None and rank == 0:
+            print(presample_line(presample, ev_train.event_shape, pooled), flush=True)
     else:
         nspe = 1 + (frames - cfg.dataset.seq_len) // cfg.dataset.stride
         ev_train = synth.blob_events(max(2, (B * 10 * world) // nspe + 1), size, frames, seed=1234)
@@ -71,7 +80,8 @@ def main(argv=None):
 
     dm = SEVIRLightningDataModule(ev_train, ev_test, dataset_name=cfg.dataset.name, num_workers=cfg.dataset.num_workers,
                                   batch_size=B, seq_len=cfg.dataset.seq_len, stride=cfg.dataset.stride, layout="NTHW",
-                                  aug_mode=str(cfg.dataset.aug_mode), val_ratio=0.1, ret_contiguous=False, device=dev)
+                                  aug_mode=str(cfg.dataset.aug_mode), val_ratio=0.1, ret_contiguous=False, device=dev,
+                                  presample=presample)
     dm.prepare_data()
     dm.setup()
     loader = dm.train_dataloader()

@@ -2038,3 +2038,36 @@ def vil_augment_u8_to_f32(src_nhwt, xf, scale=1.0 / 255.0):
     _call("wfae_vil_augment_u8_to_f32", 0, 5 * dst.numel(), src_nhwt.data_ptr(), xf.data_ptr(), _p(dst), n, h, w, t,
           scale, _stream())
     return dst
+
+
+_POOL_MODES = {"max": 0, "mean": 1}
+
+
+def vil_pool_u8_to_f32(src_nhwt, factors, mode="max", xf=None, scale=1.0 / 255.0, offset=0.0):
+    """uint8 (N,H,W,T) -> fp32 (N,To,Ho,Wo) = scale * (u8 + offset) of every ft-th frame, pooled over fh x fw blocks:
+    mode "max" (ceil sizes; factors (2, 3, 3) make sevir_lr from raw SEVIR) or "mean" (floor sizes, avg_pool2d).  xf: None,
+    or the fp32 (N,4) rows of vil_augment_u8_to_f32, applied on the pooled grid — include/wfae.h states the arithmetic."""
+    if src_nhwt.dtype != torch.uint8 or not src_nhwt.is_cuda or not src_nhwt.is_contiguous() or src_nhwt.dim() != 4:
+        raise _lib.WfaeError("vil_pool_u8_to_f32 needs a contiguous uint8 (N,H,W,T) device tensor")
+    if mode not in _POOL_MODES:
+        raise _lib.WfaeError(f"vil_pool_u8_to_f32: mode {mode!r}, not one of {sorted(_POOL_MODES)}")
+    try:
+        ft, fh, fw = (int(f) for f in factors)
+    except (TypeError, ValueError):
+        raise _lib.WfaeError(f"vil_pool_u8_to_f32 needs three integer factors (t, h, w), got {factors!r}") from None
+    n, h, w, t = src_nhwt.shape
+    if min(ft, fh, fw) < 1 or (mode == "mean" and (fh > h or fw > w)):
+        raise _lib.WfaeError(f"vil_pool_u8_to_f32: factors {(ft, fh, fw)} on frames of {h} x {w}, mode {mode}")
+    if xf is not None and (xf.dtype != torch.float32 or not xf.is_contiguous() or tuple(xf.shape) != (n, 4)
+                           or xf.device != src_nhwt.device):
+        raise _lib.WfaeError(f"vil_pool_u8_to_f32 needs contiguous fp32 transform rows of shape ({n}, 4) on "
+                             f"{src_nhwt.device}")
+    to = -(-t // ft)
+    ho, wo = (-(-h // fh), -(-w // fw)) if mode == "max" else (h // fh, w // fw)
+    dst = torch.empty((n, to, ho, wo), dtype=torch.float32, device=src_nhwt.device)
+    if dst.numel() == 0:
+        return dst
+    _call("wfae_vil_pool_u8_to_f32", 0, src_nhwt.numel() + 4 * dst.numel(), src_nhwt.data_ptr(),
+          None if xf is None else xf.data_ptr(), _p(dst), n, h, w, t, ft, fh, fw, _POOL_MODES[mode], scale, offset,
+          _stream())
+    return dst

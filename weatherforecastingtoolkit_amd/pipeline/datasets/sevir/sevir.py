@@ -12,6 +12,8 @@ Contract reproduced (reference lines):
   * a batch is a bare tensor in the requested layout, not a dict                      :1054-1064
   * train events are shuffled once (shuffle_seed 1), test events are not              :1169, 1192
   * aug_mode "1" / "2": flips + rotation per sequence, "0": none                      :1035-1050
+  * presample / downsample_dict / rescale_method: the frame loader's, passed through (presample=(2, 3, 3) over raw
+    SEVIR is the 'sevirlr' dataset; `lr_presample` tells when it applies)
 The gather, the prefetcher and the augmentation are `sevire.sevir.SEVIRFrameLoader`'s: the host gathers uint8
 sequences, the device kernel converts, re-lays and transforms them in one pass.  Events are a uint8 array or a
 `catalog.CatalogEventStore`; the test events are whatever store the caller passes for them (the date split is the
@@ -22,7 +24,7 @@ from __future__ import annotations
 import torch
 from torch.utils.data import random_split
 
-from ..sevire.sevir import _M64, SEVIRFrameLoader, _mix64
+from ..sevire.sevir import _M64, SEVIRFrameLoader, _mix64, lr_presample  # noqa: F401  (lr_presample: for the callers)
 
 
 class SequenceBatchLoader(SEVIRFrameLoader):
@@ -30,9 +32,11 @@ class SequenceBatchLoader(SEVIRFrameLoader):
     short if the count does not divide; `shuffle_order` draws a fresh permutation of `order` per epoch."""
 
     def __init__(self, events_u8, order, batch_size, seq_len, stride, layout, shuffle_events=False, device=None,
-                 aug_mode="0", seed=0, shuffle_order=False, ret_contiguous=True):
+                 aug_mode="0", seed=0, shuffle_order=False, ret_contiguous=True, presample=None, downsample_dict=None,
+                 rescale_method="01"):
         super().__init__(events_u8, batch_size, seq_len, stride, layout, shuffle=shuffle_events, device=device,
-                         aug_mode=aug_mode, aug_seed=seed)
+                         aug_mode=aug_mode, aug_seed=seed, presample=presample, downsample_dict=downsample_dict,
+                         rescale_method=rescale_method)
         self.base_order = list(range(self.total_num_seq)) if order is None else [int(i) for i in order]
         self.seed, self.shuffle_order, self.ret_contiguous = int(seed), bool(shuffle_order), bool(ret_contiguous)
         self.set_epoch(0)
@@ -59,7 +63,7 @@ class SequenceBatchLoader(SEVIRFrameLoader):
 class SEVIRLightningDataModule:
     def __init__(self, events, test_events=None, *, seq_len=25, stride=12, layout="NTHWC", aug_mode="0",
                  ret_contiguous=True, dataset_name="sevir", val_ratio=0.1, batch_size=1, num_workers=1, seed=0,
-                 device=None):
+                 device=None, presample=None, downsample_dict=None, rescale_method="01"):
         if dataset_name not in ("sevir", "sevirlr"):
             raise ValueError(f"Wrong dataset name {dataset_name}. Must be 'sevir' or 'sevirlr'.")
         assert layout[0] == "N"
@@ -67,6 +71,7 @@ class SEVIRLightningDataModule:
         self.dataset_name, self.seq_len, self.stride, self.layout = dataset_name, seq_len, stride, layout
         self.aug_mode, self.ret_contiguous, self.val_ratio = str(aug_mode), ret_contiguous, val_ratio
         self.batch_size, self.num_workers, self.seed, self.device = batch_size, num_workers, seed, device
+        self.presample, self.downsample_dict, self.rescale_method = presample, downsample_dict, rescale_method
         self.sevir_train = self.sevir_val = self.sevir_test = None
 
     def prepare_data(self):
@@ -74,7 +79,9 @@ class SEVIRLightningDataModule:
 
     def _loader(self, events, order, **kw):
         return SequenceBatchLoader(events, order, self.batch_size, self.seq_len, self.stride, self.layout,
-                                   device=self.device, seed=self.seed, ret_contiguous=self.ret_contiguous, **kw)
+                                   device=self.device, seed=self.seed, ret_contiguous=self.ret_contiguous,
+                                   presample=self.presample, downsample_dict=self.downsample_dict,
+                                   rescale_method=self.rescale_method, **kw)
 
     def setup(self, stage=None):
         if stage in (None, "fit"):

@@ -19,6 +19,12 @@ stream) with the training step of batch i.  AWS download of the reference is out
 Train-time augmentation (`aug_mode`, the reference's SECOND loader, pipeline/datasets/sevir/sevir.py:1035-1058): one
 h-flip / v-flip / rotation per sequence, drawn on the host by `augment_params` and applied on the device inside the
 conversion kernel (`ops.vil_augment_u8_to_f32`), so the batch still crosses the bus as uint8 and is written once.
+
+Downsampling (`ops.vil_pool_u8_to_f32`, the third kernel of that family): `presample=(ft, fh, fw)` applies the reference's
+OFFLINE sevir_lr recipe (save_downsampled_dataset :575-616: frames [::ft], block max) on the fly, so a loader over raw
+384 x 384 x 49 SEVIR is, batch for batch, the loader over the 128 x 128 x 25 dataset that recipe would have written;
+`downsample_dict` is the reference's runtime option (downsample_data_dict :849-890: frames [::ft], avg_pool2d) and
+`rescale_method` its choice of scale and offset (preprocess_data_dict :749-794).
 """
 from __future__ import annotations
 
@@ -33,6 +39,55 @@ from .... import ops
 
 PREPROCESS_SCALE_01 = {"vil": 1 / 255}
 PREPROCESS_OFFSET_01 = {"vil": 0}
+PREPROCESS_SCALE_SEVIR = {"vil": 1 / 47.54}           # reference sevire/sevir.py:150-159
+PREPROCESS_OFFSET_SEVIR = {"vil": -33.44}
+RESCALE = {"01": (PREPROCESS_SCALE_01, PREPROCESS_OFFSET_01), "sevir": (PREPROCESS_SCALE_SEVIR, PREPROCESS_OFFSET_SEVIR)}
+RAW_EVENT_SHAPE = (384, 384, 49)
+LR_PRESAMPLE = (2, 3, 3)                              # save_downsampled_dataset's defaults: 384 x 384 x 49 -> 128 x 128 x 25
+
+
+def _factors(f, what):
+    try:
+        out = tuple(int(x) for x in f)
+    except (TypeError, ValueError):
+        out = ()
+    if len(out) != 3 or min(out) < 1 or any(o != x for o, x in zip(out, f)):
+        raise ValueError(f"{what}: three integer factors (t, h, w) >= 1, got {f!r}")
+    return out
+
+
+def lr_presample(dataset_name, event_shape):
+    """the factors that turn the events at hand into what `dataset_name` means: (2, 3, 3) for a sevir_lr / sevirlr config
+    over raw SEVIR events (384, 384, 49), None in every other case (a store that is already low-resolution, full SEVIR)"""
+    if dataset_name in ("sevir_lr", "sevirlr") and tuple(event_shape) == RAW_EVENT_SHAPE:
+        return LR_PRESAMPLE
+    return None
+
+
+def parse_presample(text):
+    """--presample of the entry points: 'auto' -> "auto", 'none' -> None, 'T,H,W' -> (T, H, W)"""
+    t = str(text).strip().lower()
+    if t == "auto":
+        return "auto"
+    if t == "none":
+        return None
+    try:
+        return _factors([int(x) for x in t.split(",")], "--presample")
+    except ValueError:
+        raise ValueError(f"--presample: 'auto', 'none' or three integers T,H,W >= 1, got {text!r}") from None
+
+
+def resolve_presample(arg, dataset_name, event_shape):
+    """(factors or None, pooled (H, W, T)) for a parsed --presample and the events of a store"""
+    f = lr_presample(dataset_name, event_shape) if arg == "auto" else arg
+    if f is None:
+        return None, tuple(event_shape)
+    h, w, t = event_shape
+    return f, (-(-h // f[1]), -(-w // f[2]), -(-t // f[0]))
+
+
+def presample_line(factors, raw_shape, pooled_shape):
+    return "presample {}: {}x{}x{} -> {}x{}x{}".format(tuple(factors), *raw_shape, *pooled_shape)
 
 
 # out_layout values of the reference's change_layout_torch (sevire/sevir.py:98-139).  The device kernel writes the frames
@@ -121,7 +176,17 @@ def transform_rows(params):
 
 class SEVIRFrameLoader:
     def __init__(self, events_u8, batch_size, seq_len=1, stride=1, layout="NTHW", shuffle=False,
-                 shuffle_seed=1, device=None, num_shard=1, rank=0, aug_mode="0", aug_seed=0):
+                 shuffle_seed=1, device=None, num_shard=1, rank=0, aug_mode="0", aug_seed=0, presample=None,
+                 downsample_dict=None, rescale_method="01"):
+        if presample is not None and downsample_dict is not None:
+            raise NotImplementedError("presample and downsample_dict together: no reference config uses downsample_dict")
+        if rescale_method not in RESCALE:
+            raise ValueError(f"Invalid rescale option: {rescale_method}.")
+        if downsample_dict is not None and set(downsample_dict) != {"vil"}:
+            raise NotImplementedError(f"downsample_dict for {sorted(downsample_dict)}: only 'vil' is loaded")
+        self.presample = None if presample is None else _factors(presample, "presample")
+        self.downsample = None if downsample_dict is None else _factors(downsample_dict["vil"], "downsample_dict['vil']")
+        self.rescale_method = rescale_method
         if layout not in LAYOUTS:
             raise NotImplementedError(f"layout {layout!r}: the reference's change_layout_torch knows {sorted(LAYOUTS)}")
         if str(aug_mode) not in AUG_MODES:
@@ -132,7 +197,7 @@ class SEVIRFrameLoader:
             # an event store (catalog + files): events are read on demand; shuffling is the catalog's job
             self.store, self.events = events_u8, None
             self.n_events = len(events_u8)
-            self.raw_seq_len = events_u8.event_shape[2]
+            self.raw_frames = events_u8.event_shape[2]
         else:
             ev = np.ascontiguousarray(events_u8)
             assert ev.dtype == np.uint8 and ev.ndim == 4, "events must be uint8 (N_ev, H, W, T)"
@@ -140,7 +205,9 @@ class SEVIRFrameLoader:
                 ev = ev[np.random.RandomState(shuffle_seed).permutation(ev.shape[0])]
             self.store, self.events = None, ev
             self.n_events = ev.shape[0]
-            self.raw_seq_len = ev.shape[3]
+            self.raw_frames = ev.shape[3]
+        # with presample the dataset is the low-resolution one: its frames are the raw frames 0, ft, 2 ft, ...
+        self.raw_seq_len = self.raw_frames if self.presample is None else -(-self.raw_frames // self.presample[0])
         self._cache = {}
         self.batch_size, self.seq_len, self.stride = int(batch_size), int(seq_len), int(stride)
         self.device = torch.device(device) if device is not None else None
@@ -193,19 +260,37 @@ class SEVIRFrameLoader:
 
     def _convert(self, u8_dev, rows_dev):
         """device uint8 'NHWT' batch (+ transform rows unless aug_mode is "0") -> the batch the loader yields"""
-        if rows_dev is None:
-            x = ops.vil_u8_to_f32(u8_dev, PREPROCESS_SCALE_01["vil"])
+        factors, mode = (self.presample, "max") if self.presample else (self.downsample, "mean")
+        if factors is None and self.rescale_method == "01":
+            if rows_dev is None:
+                x = ops.vil_u8_to_f32(u8_dev, PREPROCESS_SCALE_01["vil"])
+            else:
+                x = ops.vil_augment_u8_to_f32(u8_dev, rows_dev, PREPROCESS_SCALE_01["vil"])
         else:
-            x = ops.vil_augment_u8_to_f32(u8_dev, rows_dev, PREPROCESS_SCALE_01["vil"])
+            scale, offset = RESCALE[self.rescale_method]
+            x = ops.vil_pool_u8_to_f32(u8_dev, factors or (1, 1, 1), mode, rows_dev, scale["vil"], offset["vil"])
         return self._wrap(LAYOUTS[self.layout](x))
+
+    @staticmethod
+    def process_data_dict_back(data_dict, data_types=None, rescale="01"):
+        """undo the preprocessing (reference :797-826): x / scale - offset, on whatever device the tensors are on"""
+        if rescale not in RESCALE:
+            raise ValueError(f"Invalid rescale option: {rescale}.")
+        scale, offset = RESCALE[rescale]
+        for key in (data_dict.keys() if data_types is None else data_types):
+            data_dict[key] = data_dict[key].float() / scale[key] - offset[key]
+        return data_dict
 
     def _wrap(self, x):
         return {"vil": x}
 
     def batch_u8(self, index):
-        """uint8 (B, H, W, seq_len) host batch, before preprocessing."""
+        """uint8 (B, H, W, seq_len) host batch, before preprocessing: what crosses the bus.  With presample it is the raw
+        span under the sequence, (B, H, W, ft * (seq_len - 1) + 1) from raw frame ft * seq_idx * stride."""
         idx = self.sample_indices(index * self.num_shard + self.rank)
-        return np.stack([self._event(e)[:, :, s * self.stride:s * self.stride + self.seq_len] for e, s in idx], 0)
+        ft = 1 if self.presample is None else self.presample[0]
+        span = ft * (self.seq_len - 1) + 1
+        return np.stack([self._event(e)[:, :, ft * s * self.stride:ft * s * self.stride + span] for e, s in idx], 0)
 
     def _event(self, e):
         if self.events is not None:
