@@ -9,26 +9,21 @@ the step (:161-167) takes nn.HuberLoss between that reconstruction and the laten
 Each of the seven units is ONE gfx950 launch forward (csrc/convae.hip: one workgroup holds a sample's convolution
 output in LDS from the convolution to the activation) and one entry point backward.  The torch module classes are kept
 as parameter containers, built and initialised in the reference's order, so state_dict keys / order / shapes and the
-seeded initial values are the reference's.
+seeded initial values are the reference's.  The frozen latent provider is ./_latents.py; the optimiser step and the
+driver are the v1 experiments' shared ones (./_runner.py).
 """
 from __future__ import annotations
-
-import argparse
-import json
-import os
-import time
 
 import torch
 import torch.nn as tnn
 
-from ... import config as C
 from ... import functional as Fn
 from ... import nn as wnn
-from ... import ops, parallel, synth
+from ... import ops
 from ..._lib import WfaeError
 from ...pipeline import helpers
-from ...pipeline.datasets.sevire.sevir import SEVIRFrameLoader
-from ._dlinear import Autoencoder  # noqa: F401  (the frozen latent provider; it already decodes)
+from ._latents import Autoencoder  # noqa: F401  (the frozen latent provider)
+from ._runner import Step
 
 CLN_MAX_CIN, CLN_MAX_COUT, CLN_MAX_ELEMS = 64, 16, 18432   # served range of the fused unit (include/wfae.h)
 
@@ -128,8 +123,11 @@ class ConvModel(tnn.Module):
         return z, self.decoder(y).reshape(b, t, c, h, w)
 
 
-class Model(tnn.Module):
-    """reference Model (:145-207): `predictor`, `forward`, the training / validation / test steps and the optimiser"""
+class Model(Step, tnn.Module):
+    """reference Model (:145-207): `predictor`, `forward`, the training / validation / test steps; the optimiser is
+    `Step`'s, with the exact complements of FusedAdamW"""
+
+    exact_complements = True
 
     def __init__(self, cfg, autoencoder=None):
         super().__init__()
@@ -150,50 +148,24 @@ class Model(tnn.Module):
         pred = self(v)
         return Fn.huber_loss(pred, v, self.delta), pred
 
-    def _frames_latents(self, batch):
-        """-> (frames (B, T, 1, H, W) or None, latents (B, T, C, h, w))"""
-        if isinstance(batch, dict):
-            batch = batch["vil"]
-        if batch.dim() == 4:
-            if self.autoencoder is None:
-                raise WfaeError("a batch of frames (B, T, H, W) needs the frozen autoencoder; pass latents "
-                                "(B, T, C, h, w) or construct Model(cfg, autoencoder=...)")
-            frames = batch.unsqueeze(2)
-            return frames, self.autoencoder.encode(frames)
-        return None, batch
-
     def _metric_interval(self, split):
         """the reference's metric cadence: every int(logging.log_<split>_all_metrics_n * total steps) batches"""
         lg = self.cfg.get("logging") or {}
         n = lg.get(f"log_{'train' if split == 'train' else 'val'}_all_metrics_n", 0) or 0
         return max(1, int(n * max(self.total_steps, 1)))
 
-    def configure_optimizers(self):
-        o, sp = self.cfg.optim, self.cfg.cosine_warmup
-        self.opt = helpers.adamw_optimizer(self.predictor, o.lr, o.weight_decay, exact_complements=True)
-        self.sch = helpers.cosine_warmup_scheduler(self.opt, sp.start_lr, sp.final_lr, sp.peak_lr, self.total_steps,
-                                                   sp.warmup_ratio * self.total_steps)
-        self._dp = parallel.DataParallelTrainer(self.predictor, self.opt)
-        return self.opt
-
     def training_step(self, batch, batch_idx=0):
         """batch: frames (B, T, H, W) fp32 in [0, 1] ('NTHW') or latents (B, T, C, h, w); AdamW + cosine warmup, the
         gradient norm clipped at optim.gradient_clip_val.  -> (loss, gradient norm before clipping)"""
-        _, v = self._frames_latents(batch)
+        _, v = self.frames_latents(batch)
         loss, _ = self.latent_loss(v)
-        loss.backward()
-        self._dp.reduce_gradients()
-        gn = self.opt.clip_grad_norm_(self.cfg.optim.gradient_clip_val)
-        self.opt.step()
-        self.sch.step()
-        self.opt.zero_grad(set_to_none=True)
-        return loss.detach(), gn
+        return self.optimizer_step(loss)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0, split="val"):
         """-> (loss, logs): logs holds `{split}_loss` and, for a batch of frames with a provider that decodes, the
         `{split}_` calc_metrics keys of the decoded reconstruction against the input frames (reference :189-192)"""
-        frames, v = self._frames_latents(batch)
+        frames, v = self.frames_latents(batch)
         loss, pred = self.latent_loss(v)
         logs = {f"{split}_loss": loss}
         ae = self.autoencoder
@@ -204,66 +176,3 @@ class Model(tnn.Module):
 
     def test_step(self, batch, batch_idx=0):
         return self.validation_step(batch, 0, split="test")
-
-
-def main(here, default_mode, argv=None):
-    """`--mode fit` trains (AdamW, cosine warmup, clip) and writes `last.ckpt` with `predictor.`-prefixed keys in the
-    reference's layout; `--mode test` runs test_step over the loader"""
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default=os.path.join(here, "config.yaml"))
-    ap.add_argument("--max-steps", type=int, default=-1)
-    ap.add_argument("--mode", choices=("fit", "test"), default=default_mode)
-    args, unknown = ap.parse_known_args(argv)
-    cfg = C.load(args.config)
-    cli = C.from_dotlist(unknown)
-    helpers.check_yaml(cfg, cli)
-    cfg = C.merge(cfg, cli)
-    rank, world, local = parallel.init_from_env()
-    dev = torch.device("cuda", local)
-    torch.cuda.set_device(dev)
-    size, frames = (384, 49) if cfg.dataset.name == "sevir" else (128, 25)
-    events = synth.blob_events(max(2, cfg.dataset.batch_size * 2 * world), size, frames, seed=1234)
-    loader = SEVIRFrameLoader(events, cfg.dataset.batch_size, cfg.dataset.seq_len, cfg.dataset.stride, "NTHW",
-                              shuffle=args.mode == "fit", device=dev, num_shard=world, rank=rank)
-    total = max(1, int(len(loader) * cfg.trainer.max_epochs / cfg.trainer.accumulate_grad_batches))
-    if args.mode == "test":
-        total = len(loader)
-    if 0 < args.max_steps < total:
-        total = args.max_steps
-    cfg.trainer.total_train_steps = total
-    torch.manual_seed(0)
-    model = Model(cfg, autoencoder=Autoencoder(size, cfg.autoencoder.kind, cfg.autoencoder)).to(dev).train()
-    model.autoencoder.eval()
-    step, t0 = 0, time.time()
-    if args.mode == "test":
-        model.eval()
-        for batch in loader:
-            if step >= total:
-                break
-            loss, logs = model.test_step(batch["vil"], step)
-            step += 1
-            if rank == 0:
-                print(json.dumps({"step": step, **{k: float(v) for k, v in logs.items()}}), flush=True)
-        if rank == 0:
-            print("done")
-        return 0
-    model.configure_optimizers()
-    while step < total:
-        for batch in loader:
-            if step >= total:
-                break
-            loss, gn = model.training_step(batch["vil"])
-            step += 1
-            if rank == 0 and step % max(1, cfg.trainer.log_every_n_steps) == 0:
-                print(json.dumps({"step": step, "train_loss": float(loss), "grad_norm": float(gn),
-                                  "lr": model.opt.param_groups[0]["lr"],
-                                  "frames_per_s": step * cfg.dataset.batch_size * cfg.dataset.seq_len * world
-                                  / (time.time() - t0)}), flush=True)
-    if rank == 0:
-        out = os.path.join(cfg.experiment_path, "outputs", cfg.experiment_name, "checkpoints")
-        os.makedirs(out, exist_ok=True)
-        torch.save({"state_dict": {"predictor." + k: v.detach().cpu().clone()
-                                   for k, v in model.predictor.state_dict().items()},
-                    "global_step": step}, os.path.join(out, "last.ckpt"))
-        print("done")
-    return 0

@@ -11,26 +11,22 @@ Here the latent sequence v (B, T, C, h, w) is viewed as rows (B, T*cf, M): cf = 
 The whole predictor step is a handful of gfx950 kernels (csrc/dlinear.hip): target, fused differencing +
 decomposition + both linear maps, MSE, the weight gradients, clip and AdamW — instead of the reference's Python loop
 over 9216 (or 2304) module pairs.  Parameters are stacked (M, P, L) tensors; state_dict() / load_state_dict() speak
-the reference's per-module keys.
+the reference's per-module keys.  The frozen latent provider is ./_latents.py; the optimiser step and the driver are
+the v1 experiments' shared ones (./_runner.py).
 """
 from __future__ import annotations
 
-import argparse
-import json
 import math
-import os
-import time
 
 import torch
 import torch.nn as tnn
 
-from ... import config as C
 from ... import functional as Fn
-from ... import ops, parallel, synth
+from ... import ops
 from ..._lib import WfaeError
 from ...pipeline import helpers
-from ...pipeline.datasets.sevire.sevir import SEVIRFrameLoader
-from .pretrained_ae_linear_sevir.train import Autoencoder as _LatentEncoder
+from ._latents import Autoencoder  # noqa: F401  (the frozen latent provider)
+from ._runner import Step
 
 
 def _check_kernel_size(kernel_size):
@@ -196,30 +192,9 @@ class DLinear(tnn.Module):
         return self._apply_rows(v, True)
 
 
-class Autoencoder(_LatentEncoder):
-    """frozen latent provider of the DLinear experiments: the linear experiment's encoder (pretrained_ae_linear_sevir)
-    plus, for the conv kind, `decode` — act(dec(z)) for each frame — so that validation / test can score forecasts in
-    frame space like the reference (:196-200)."""
-
-    def can_decode(self):
-        return self.kind in ("ae_64x8x8_lin.enc", "autoencoder_kl")
-
-    @torch.no_grad()
-    def decode(self, z):
-        """z (B, T, C, h, w) -> frames (B, T, 1, H, W)"""
-        if not self.can_decode():
-            raise WfaeError(f"Autoencoder.decode: kind {self.kind!r} has no decoder")
-        b, t = z.shape[:2]
-        ae = self.autoencoder
-        if self.kind == "autoencoder_kl":
-            x = torch.cat([ae.decode(f) for f in self._chunks(z.reshape(b * t, *z.shape[2:]))])
-            return x.view(b, t, *x.shape[1:])
-        x = ae.act(ae.dec(z.reshape(b * t, *z.shape[2:]).contiguous()))
-        return x.view(b, t, *x.shape[1:])
-
-
-class Model(tnn.Module):
-    """reference Model (:137-239): `predictor`, `forward`, the training / validation / test steps and the optimiser"""
+class Model(Step, tnn.Module):
+    """reference Model (:137-239): `predictor`, `forward`, the training / validation / test steps; the optimiser is
+    `Step`'s"""
 
     def __init__(self, cfg, autoencoder=None):
         super().__init__()
@@ -260,13 +235,6 @@ class Model(tnn.Module):
         tgt = ops.dlinear_target(rows, L, P, f)
         return Fn.mse_loss(pred, tgt), pred, rows
 
-    def _latents(self, batch):
-        if isinstance(batch, dict):
-            batch = batch["vil"]
-        if batch.dim() == 4:
-            return self.autoencoder.encode(batch.unsqueeze(2))
-        return batch
-
     @torch.no_grad()
     def predict_latents(self, v):
         """forecast latents (B, Tout, C, h, w) = pred + last input frame (reference :197)"""
@@ -276,31 +244,17 @@ class Model(tnn.Module):
         return ops.dlinear_forecast(pred, rows, self.predictor.in_rows, self.predictor.features).view(
             b, self.pred_frames, c, h, w)
 
-    def configure_optimizers(self):
-        o, sp = self.cfg.optim, self.cfg.cosine_warmup
-        self.opt = helpers.adamw_optimizer(self.predictor, o.lr, o.weight_decay)
-        self.sch = helpers.cosine_warmup_scheduler(self.opt, sp.start_lr, sp.final_lr, sp.peak_lr, self.total_steps,
-                                                   sp.warmup_ratio * self.total_steps)
-        self._dp = parallel.DataParallelTrainer(self.predictor, self.opt)
-        return self.opt
-
     def training_step(self, batch, batch_idx=0):
         """batch: frames (B,T,H,W) fp32 in [0,1] ('NTHW') or latents (B,T,C,h,w); AdamW + cosine warmup, clip 1.0"""
-        v = self._latents(batch)
+        _, v = self.frames_latents(batch)
         loss, _, _ = self.latent_loss(v)
-        loss.backward()
-        self._dp.reduce_gradients()
-        gn = self.opt.clip_grad_norm_(self.cfg.optim.gradient_clip_val)
-        self.opt.step()
-        self.sch.step()
-        self.opt.zero_grad(set_to_none=True)
-        return loss.detach(), gn
+        return self.optimizer_step(loss)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0, split="val"):
         """-> (loss, logs): logs holds `{split}_loss` and, when the provider decodes, the `{split}_` calc_metrics keys
         of the decoded forecast against the decoded target (reference :180-203)"""
-        v = self._latents(batch)
+        _, v = self.frames_latents(batch)
         loss, pred, rows = self.latent_loss(v)
         logs = {f"{split}_loss": loss}
         ae = self.autoencoder
@@ -316,65 +270,3 @@ class Model(tnn.Module):
     def test_step(self, batch, batch_idx=0):
         return self.validation_step(batch, batch_idx, split="test")
 
-
-def main(here, default_mode, argv=None):
-    """shared driver of the three experiments: `--mode fit` trains (AdamW, cosine warmup, clip 1.0) and writes
-    `last.ckpt` in the reference's key layout; `--mode test` runs test_step over the loader"""
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default=os.path.join(here, "config.yaml"))
-    ap.add_argument("--max-steps", type=int, default=-1)
-    ap.add_argument("--mode", choices=("fit", "test"), default=default_mode)
-    args, unknown = ap.parse_known_args(argv)
-    cfg = C.load(args.config)
-    cli = C.from_dotlist(unknown)
-    helpers.check_yaml(cfg, cli)
-    cfg = C.merge(cfg, cli)
-    rank, world, local = parallel.init_from_env()
-    dev = torch.device("cuda", local)
-    torch.cuda.set_device(dev)
-    size, frames = (384, 49) if cfg.dataset.name == "sevir" else (128, 25)
-    events = synth.blob_events(max(2, cfg.dataset.batch_size * 2 * world), size, frames, seed=1234)
-    loader = SEVIRFrameLoader(events, cfg.dataset.batch_size, cfg.dataset.seq_len, cfg.dataset.stride, "NTHW",
-                              shuffle=args.mode == "fit", device=dev, num_shard=world, rank=rank)
-    total = max(1, int(len(loader) * cfg.trainer.max_epochs / cfg.trainer.accumulate_grad_batches))
-    if args.mode == "test":
-        total = len(loader)
-    if 0 < args.max_steps < total:
-        total = args.max_steps
-    cfg.trainer.total_train_steps = total
-    torch.manual_seed(0)
-    model = Model(cfg, autoencoder=Autoencoder(size, cfg.autoencoder.kind, cfg.autoencoder)).to(dev).train()
-    model.autoencoder.eval()
-    step, t0 = 0, time.time()
-    if args.mode == "test":
-        model.eval()
-        for batch in loader:
-            if step >= total:
-                break
-            loss, logs = model.test_step(batch["vil"], step)
-            step += 1
-            if rank == 0:
-                print(json.dumps({"step": step, **{k: float(v) for k, v in logs.items()}}), flush=True)
-        if rank == 0:
-            print("done")
-        return 0
-    model.configure_optimizers()
-    while step < total:
-        for batch in loader:
-            if step >= total:
-                break
-            loss, gn = model.training_step(batch["vil"])
-            step += 1
-            if rank == 0 and step % max(1, cfg.trainer.log_every_n_steps) == 0:
-                print(json.dumps({"step": step, "train_loss": float(loss), "grad_norm": float(gn),
-                                  "lr": model.opt.param_groups[0]["lr"],
-                                  "sequences_per_s": step * cfg.dataset.batch_size * world / (time.time() - t0)}),
-                      flush=True)
-    if rank == 0:
-        out = os.path.join(cfg.experiment_path, "outputs", cfg.experiment_name, "checkpoints")
-        os.makedirs(out, exist_ok=True)
-        torch.save({"state_dict": {"predictor." + k: v.detach().cpu().clone()
-                                   for k, v in model.predictor.state_dict().items()},
-                    "global_step": step}, os.path.join(out, "last.ckpt"))
-        print("done")
-    return 0

@@ -1,0 +1,104 @@
+"""Frozen latent provider of the v1 latent experiments (linear, DLinear, conv autoencoder): the reference's `Autoencoder`
+wrapper around a pretrained AutoencoderKL (pretrained_ae_linear_sevir/train.py:21-56, the same class in the DLinear and
+conv experiments), with the project's own encoders as further kinds.  The experiments' `train.py` and `_dlinear.py`
+re-export it under the name `Autoencoder`.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as tnn
+
+from ..._lib import WfaeError
+from ...pipeline.models.ae_64x8x8_lin import PosAwareAE_TF
+
+
+class Autoencoder(tnn.Module):
+    """frozen latent provider with the reference wrapper's interface (:21-56): encode (B,T,1,H,W) -> (B,T,C,h,w).
+    kind "ae_64x8x8_lin.enc": the conv encoder stack (64 channels at 1/16 resolution);
+    kind "ae_vit.tokens": the structured token latent [64, 512] of AE_ViT_2048 (BASELINE config 4), i.e. the
+    encoder tokens laid out as 512 channels on the 8x8 patch grid;
+    kind "autoencoder_kl": the reference's own provider, the frozen AutoencoderKL (pipeline/models/autoencoderkl) built
+    from the `autoencoder:` config block `cfg` (the reference's keys), with `cfg.checkpoint` loaded when given (a state
+    dict, or a Lightning checkpoint that holds it under the `autoencoder.` / `model.` prefix, other modules' keys next to
+    it being ignored), else a seeded initialisation
+    (`cfg.seed`, default 0).  encode returns the posterior's mode; frames go through in chunks of `cfg.chunk_frames`.
+    The conv and AutoencoderKL kinds also `decode` — act(dec(z)) for each frame — so that validation / test can score
+    forecasts in frame space like the reference (pretrained_ae_dlinear_*/train.py:196-200)."""
+
+    AEKL_KEYS = ("in_channels", "out_channels", "down_block_types", "up_block_types", "block_out_channels",
+                 "layers_per_block", "act_fn", "latent_channels", "norm_num_groups", "sample_size", "scaling_factor")
+
+    def __init__(self, img_size=128, kind="ae_64x8x8_lin.enc", cfg=None):
+        super().__init__()
+        self.kind = kind
+        self.chunk_frames = 0
+        if kind == "autoencoder_kl":
+            self.autoencoder = self._build_autoencoder_kl(cfg or {})
+            self.chunk_frames = int((cfg or {}).get("chunk_frames") or 8)
+            if self.chunk_frames < 1:
+                raise ValueError(f"autoencoder.chunk_frames={self.chunk_frames}")
+        elif kind == "ae_vit.tokens":
+            from ...pipeline.models.ae_vit import AE_ViT_2048
+            self.autoencoder = AE_ViT_2048().eval()
+        elif kind == "ae_64x8x8_lin.enc":
+            self.autoencoder = PosAwareAE_TF(img_size=img_size).eval()
+        else:
+            raise ValueError(f"autoencoder.kind={kind!r}")
+        for p in self.autoencoder.parameters():
+            p.requires_grad_(False)
+
+    @classmethod
+    def _build_autoencoder_kl(cls, cfg):
+        from ...pipeline.models.autoencoderkl import AutoencoderKL
+        kw = {k: cfg[k] for k in cls.AEKL_KEYS if cfg.get(k) is not None}
+        ckpt = cfg.get("checkpoint")
+        if ckpt:
+            model = AutoencoderKL(**kw)
+            sd = torch.load(ckpt, map_location="cpu")
+            sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+            # a Lightning checkpoint holds the provider under a prefix, next to other modules (predictor.*, loss.*): keep
+            # the keys under the first prefix that holds the VAE, drop the rest; the strict load then checks what is kept
+            probe = "encoder.conv_in.weight"
+            for prefix in ("", "autoencoder.autoencoder.", "autoencoder.", "model."):
+                if prefix + probe in sd:
+                    sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)} if prefix else sd
+                    break
+            model.load_state_dict(sd, strict=True)
+            return model
+        with torch.random.fork_rng(devices=[]):     # the seeded initialisation does not move the caller's generator
+            torch.manual_seed(int(cfg.get("seed") or 0))
+            return AutoencoderKL(**kw)
+
+    def _chunks(self, frames):
+        n = self.chunk_frames if self.chunk_frames > 0 else frames.shape[0]
+        return [frames[i:i + n].contiguous() for i in range(0, frames.shape[0], n)]
+
+    @torch.no_grad()
+    def encode(self, x):
+        b, t, c, h, w = x.shape
+        frames = x.reshape(b * t, c, h, w)
+        if self.kind == "autoencoder_kl":
+            z = torch.cat([self.autoencoder.encode(f).mode() for f in self._chunks(frames)])
+        elif self.kind == "ae_vit.tokens":
+            tok = self.autoencoder.encode_tokens(frames)                      # (B*T, 64, 512)
+            s = self.autoencoder.seq
+            z = tok.transpose(1, 2).contiguous().view(b * t, tok.shape[2], s, s)
+        else:
+            z = self.autoencoder.enc(frames)
+        return z.view(b, t, *z.shape[1:])
+
+    def can_decode(self):
+        return self.kind in ("ae_64x8x8_lin.enc", "autoencoder_kl")
+
+    @torch.no_grad()
+    def decode(self, z):
+        """z (B, T, C, h, w) -> frames (B, T, 1, H, W)"""
+        if not self.can_decode():
+            raise WfaeError(f"Autoencoder.decode: kind {self.kind!r} has no decoder")
+        b, t = z.shape[:2]
+        ae = self.autoencoder
+        if self.kind == "autoencoder_kl":
+            x = torch.cat([ae.decode(f) for f in self._chunks(z.reshape(b * t, *z.shape[2:]))])
+            return x.view(b, t, *x.shape[1:])
+        x = ae.act(ae.dec(z.reshape(b * t, *z.shape[2:]).contiguous()))
+        return x.view(b, t, *x.shape[1:])

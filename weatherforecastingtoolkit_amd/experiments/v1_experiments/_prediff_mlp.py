@@ -9,26 +9,21 @@ clip 1.0.
 Here a training step is: one read of the batch for all 13 statistics (two launches of csrc/prediff.hip, in the memory
 order the loader delivers, no copy), one launch for the MLP forward + loss + all six gradients, then scale, clip and
 AdamW over the flat arenas.  `torch.compile` only renames the reference's checkpoint keys (`model._orig_mod.mlp.N.*`):
-state_dict() writes that spelling, load_state_dict() takes it and the plain `model.mlp.N.*`.
+state_dict() writes that spelling, load_state_dict() takes it and the plain `model.mlp.N.*`.  The optimiser step and
+the driver are the v1 experiments' shared ones (./_runner.py).
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import time
 from collections import OrderedDict
 
 import torch
 import torch.nn as tnn
 
-from ... import config as C
 from ... import functional as Fn
 from ... import nn as wnn
-from ... import ops, parallel, synth
+from ... import ops
 from ..._lib import WfaeError
-from ...pipeline import helpers
-from ...pipeline.datasets.sevire.sevir import SEVIRFrameLoader
+from ._runner import Step
 
 GROUPS = 4   # the reference's `reshape(b, 4, t // 4, -1)`
 _COMPILED = "model._orig_mod."
@@ -68,8 +63,11 @@ class MLP(tnn.Module):
         return Fn.mlp3_mse_loss(x, target, *self.parameters_in_order())
 
 
-class Model(tnn.Module):
-    """reference Model (:40-95): `model` (the MLP), forward, the training / validation steps and the optimiser"""
+class Model(Step, tnn.Module):
+    """reference Model (:40-95): `model` (the MLP), forward, the training / validation steps; the optimiser is `Step`'s,
+    on `model`"""
+
+    trained = "model"
 
     def __init__(self, cfg, mlp=None):
         super().__init__()
@@ -119,74 +117,14 @@ class Model(tnn.Module):
                             f"{tuple(batch.shape)}")
         return ops.seq_intensity_stats(batch, self.input_frames, GROUPS)
 
-    def configure_optimizers(self):
-        o, sp = self.cfg.optim, self.cfg.cosine_warmup
-        self.opt = helpers.adamw_optimizer(self.model, o.lr, o.weight_decay)
-        self.sch = helpers.cosine_warmup_scheduler(self.opt, sp.start_lr, sp.final_lr, sp.peak_lr, self.total_steps,
-                                                   sp.warmup_ratio * self.total_steps)
-        self._dp = parallel.DataParallelTrainer(self.model, self.opt)
-        return self.opt
-
     def training_step(self, batch, batch_idx=0):
         """batch: 'NHWT' frames (B, H, W, T) fp32 in [0, 1]; AdamW + cosine warmup, clip 1.0 -> (loss, grad norm)"""
         x, target = self.statistics(batch)
         loss, _ = self.model.loss(x, target)
-        loss.backward()
-        self._dp.reduce_gradients()
-        gn = self.opt.clip_grad_norm_(self.cfg.optim.gradient_clip_val)
-        self.opt.step()
-        self.sch.step()
-        self.opt.zero_grad(set_to_none=True)
-        return loss.detach(), gn
+        return self.optimizer_step(loss)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0):
         """-> val_loss (reference :72-84)"""
         x, target = self.statistics(batch)
         return ops.mlp3_mse(x, target, *[p.detach() for p in self.model.parameters_in_order()])[1]
-
-
-def main(here, argv=None):
-    """`fit` of the reference's `__main__`: trains on synthetic blob events through the 'NHWT' loader and writes
-    `last.ckpt` in the reference's key layout"""
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default=os.path.join(here, "config.yaml"))
-    ap.add_argument("--max-steps", type=int, default=-1)
-    args, unknown = ap.parse_known_args(argv)
-    cfg = C.load(args.config)
-    cli = C.from_dotlist(unknown)
-    helpers.check_yaml(cfg, cli)
-    cfg = C.merge(cfg, cli)
-    rank, world, local = parallel.init_from_env()
-    dev = torch.device("cuda", local)
-    torch.cuda.set_device(dev)
-    size, frames = (384, 49) if cfg.dataset.name == "sevir" else (128, 25)
-    events = synth.blob_events(max(2, cfg.dataset.batch_size * 2 * world), size, frames, seed=1234)
-    loader = SEVIRFrameLoader(events, cfg.dataset.batch_size, cfg.dataset.seq_len, cfg.dataset.stride,
-                              cfg.dataset.layout, shuffle=True, device=dev, num_shard=world, rank=rank)
-    total = max(1, int(len(loader) * cfg.trainer.max_epochs / cfg.trainer.accumulate_grad_batches))
-    if 0 < args.max_steps < total:
-        total = args.max_steps
-    cfg.trainer.total_train_steps = total
-    torch.manual_seed(0)
-    model = Model(cfg).to(dev).train()
-    model.configure_optimizers()
-    step, t0 = 0, time.time()
-    while step < total:
-        for batch in loader:
-            if step >= total:
-                break
-            loss, gn = model.training_step(batch["vil"])
-            step += 1
-            if rank == 0 and step % max(1, cfg.trainer.log_every_n_steps) == 0:
-                print(json.dumps({"step": step, "train_loss": float(loss), "grad_norm": float(gn),
-                                  "lr": model.opt.param_groups[0]["lr"],
-                                  "sequences_per_s": step * cfg.dataset.batch_size * world / (time.time() - t0)}),
-                      flush=True)
-    if rank == 0:
-        out = os.path.join(cfg.experiment_path, "outputs", cfg.experiment_name, "checkpoints")
-        os.makedirs(out, exist_ok=True)
-        torch.save({"state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
-                    "global_step": step}, os.path.join(out, "last.ckpt"))
-        print("done")
-    return 0

@@ -4,7 +4,7 @@ frames -> Linear(5, 128)-ReLU-Linear(128, 128)-ReLU-Linear(128, 8) -> mean and s
 
     python -m weatherforecastingtoolkit_amd.experiments.v1_experiments.prediff_mlp_sevir.train [--max-steps N] key=value ...
 
-MLP, Model and the driver live in ../_prediff_mlp.py.
+MLP and Model live in ../_prediff_mlp.py, the driver in ../_runner.py.
 """
 from __future__ import annotations
 
@@ -12,13 +12,14 @@ import os
 import sys
 
 from .._prediff_mlp import MLP, Model  # noqa: F401
-from .._prediff_mlp import main as _main
+from .._runner import run
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def main(argv=None):
-    return _main(HERE, argv)
+    return run(HERE, argv, lambda cfg, size: Model(cfg), layout=lambda cfg: cfg.dataset.layout,
+               state=lambda model: model.state_dict())
 
 
 if __name__ == "__main__":

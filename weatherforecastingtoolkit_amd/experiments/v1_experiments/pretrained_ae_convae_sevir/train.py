@@ -4,7 +4,8 @@ auto-encoded by a small conv network (conv + LayerNorm over the sample + LeakyRe
 
     python -m weatherforecastingtoolkit_amd.experiments.v1_experiments.pretrained_ae_convae_sevir.train [--mode fit|test] key=value ...
 
-The default mode is `fit`, as the reference's `__main__` calls `trainer.fit`.  The classes live in ../_convae.py.
+The default mode is `fit`, as the reference's `__main__` calls `trainer.fit`.  The classes live in ../_convae.py, the
+driver in ../_runner.py.
 """
 from __future__ import annotations
 
@@ -12,13 +13,13 @@ import os
 import sys
 
 from .._convae import Autoencoder, ConvDecoder, ConvEncoder, ConvModel, Model  # noqa: F401
-from .._convae import main as _main
+from .._runner import run, with_provider
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def main(argv=None):
-    return _main(HERE, "fit", argv)
+    return run(HERE, argv, with_provider(Model), default_mode="fit", rate="frames_per_s")
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@ reference's experiments/v1_experiments/pretrained_ae_dlinear_sevir/train.py with
     python -m weatherforecastingtoolkit_amd.experiments.v1_experiments.pretrained_ae_dlinear_sevir.train [--mode fit|test] key=value ...
 
 The default mode is `test`, as the reference's `__main__` calls `trainer.test`.  Model, DLinear, moving_avg and
-series_decomp are shared by the three DLinear experiments (../_dlinear.py).
+series_decomp are shared by the three DLinear experiments (../_dlinear.py); the driver is ../_runner.py.
 """
 from __future__ import annotations
 
@@ -12,13 +12,13 @@ import os
 import sys
 
 from .._dlinear import Autoencoder, DLinear, Model, moving_avg, series_decomp  # noqa: F401
-from .._dlinear import main as _main
+from .._runner import run, with_provider
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def main(argv=None):
-    return _main(HERE, "test", argv)
+    return run(HERE, argv, with_provider(Model), default_mode="test")
 
 
 if __name__ == "__main__":
