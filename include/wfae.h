@@ -665,6 +665,51 @@ int wfae_aekl_softmax(const float* x, float* y, int64_t rows, int cols, float sc
 int wfae_aekl_posterior(const float* moments, const float* noise, float* mean, float* logvar, float* std_, float* sample, int N,
                         int C, int HW, wfae_stream_t stream);
 
+/* ---- LPIPS perceptual loss of the AE+GAN step (reference pipeline/models/autoencoderkl/losses/lpips.py `LPIPS`,
+ * `ScalingLayer`, `vgg16`, `normalize_tensor`, `spatial_average`; used by experiments/ae_v2_2/train.py:56-60): forward and
+ * the gradient with respect to the first image.  The VGG16 is frozen: no weight gradients.  NCHW fp32, fixed summation
+ * order, no atomics.  Added within ABI version 103; nothing changed.
+ * conv3_fwd: y (N, Cout, H, W) = max(conv3x3(x (N, Cin, H, W), stride 1, pad 1) + bias (Cout), 0).  The kernel, the modes
+ *   (1 / 3 / 4) and the packed weights are those of wfae_aekl_conv3_fwd kind 0: pack (Cout, Cin, 3, 3) with
+ *   wfae_aekl_conv3_pack(w, packed, Cout, Cin, mode).
+ * conv3_bwd_data: dx (N, Cin, H, W) = conv3x3(dy (N, Cout, H, W), w rotated 180 degrees with in / out transposed) *
+ *   (a_prev > 0); a_prev (dx's shape, may be null: no mask) is the post-ReLU activation that fed the layer, so dx is the
+ *   gradient of its pre-activation.  packed_t: w.flip(2, 3).transpose(0, 1) (Cin, Cout, 3, 3) packed with
+ *   wfae_aekl_conv3_pack(wt, packed_t, Cin, Cout, mode).
+ *   Both: channel counts 1..4096 (else WFAE_ERR_UNSUPPORTED); N, H, W >= 1, H, W <= 8192, a sample below 2^31 elements,
+ *   N * ceil(Cout / 64) <= 65535, a known mode, packed 16-byte aligned (else WFAE_ERR_BAD_SHAPE).
+ * pool_fwd: y (N, C, H / 2, W / 2) = 2 x 2 stride-2 max-pool of x (N, C, H, W), floor on odd sizes; H, W >= 2.
+ * pool_bwd: the gradient of the pool INPUT's pre-activation in one pass.  a (N, C, H, W) is the pool's input, a post-ReLU
+ *   activation; dy (N, C, H / 2, W / 2); add (a's shape, may be null) a second gradient of a (the distance gradient of the
+ *   tap):  dpre[y, x] = ((a[y, x] is the FIRST maximum of its window in the order (0,0), (0,1), (1,0), (1,1) — torch's
+ *   routing) ? dy : 0) + add[y, x], times (a[y, x] > 0).  A last odd row / column belongs to no window: add only.
+ * dist_fwd: one tap layer.  f = a / (sqrt(sum_c a^2) + 1e-10) for a0 and a1 (N, C, HW);
+ *   out[n] += 1 / HW * sum_pixels sum_c lin[c] (f0 - f1)^2  (out (N) must be initialised; ws >= dist_ws_bytes(N, HW),
+ *   8-byte aligned).  C in {64, 128, 256, 512} (else WFAE_ERR_UNSUPPORTED); N <= 65535.
+ * dist_bwd: da0 (N, C, HW) = g[n] * d out[n] / d a0 (a1 has no gradient); relu != 0: times (a0 > 0), for a tap that no
+ *   pool follows.  DEVIATION from the reference: at a pixel whose a0 is zero in every channel the reference's autograd
+ *   gives NaN (0 * inf through the square root); here the term  - a0 / ||a0|| * (...)  is dropped there and the result
+ *   is the finite  u / 1e-10.
+ * prep_fwd: y (N, 3, HW) = (x (N, Cx, HW) - shift[c]) / scale[c]; Cx = 1 (every output channel reads channel 0, the
+ *   reference's repeat(1, 3, 1, 1)) or 3 (else WFAE_ERR_UNSUPPORTED).  shift, scale: 3 device floats.
+ * prep_bwd: dx (N, Cx, HW) = dy[c] / scale[c] (Cx = 3) or (dy[0] / scale[0] + dy[1] / scale[1]) + dy[2] / scale[2].
+ * Null pointers return WFAE_ERR_NULL_POINTER, counts < 1 WFAE_ERR_BAD_SHAPE, all before any launch. */
+int wfae_lpips_conv3_fwd(const float* x, const void* packed, const float* bias, float* y, int mode, int N, int Cin, int Cout,
+                         int H, int W, wfae_stream_t stream);
+int wfae_lpips_conv3_bwd_data(const float* dy, const void* packed_t, const float* a_prev, float* dx, int mode, int N, int Cin,
+                              int Cout, int H, int W, wfae_stream_t stream);
+int wfae_lpips_pool_fwd(const float* x, float* y, int N, int C, int H, int W, wfae_stream_t stream);
+int wfae_lpips_pool_bwd(const float* a, const float* dy, const float* add, float* dpre, int N, int C, int H, int W,
+                        wfae_stream_t stream);
+size_t wfae_lpips_dist_ws_bytes(int N, int HW);
+int wfae_lpips_dist_fwd(const float* a0, const float* a1, const float* lin, float* out, int N, int C, int HW, void* ws,
+                        size_t ws_bytes, wfae_stream_t stream);
+int wfae_lpips_dist_bwd(const float* a0, const float* a1, const float* lin, const float* g, float* da0, int N, int C, int HW,
+                        int relu, wfae_stream_t stream);
+int wfae_lpips_prep_fwd(const float* x, const float* shift, const float* scale, float* y, int N, int Cx, int HW,
+                        wfae_stream_t stream);
+int wfae_lpips_prep_bwd(const float* dy, const float* scale, float* dx, int N, int Cx, int HW, wfae_stream_t stream);
+
 /* ---- sigmoid + L1 loss (ae_64x8x8_lin.py:102 + experiments/ae_v2/train.py:55)
  * recon = sigmoid(h); loss[0] = weight * mean |recon - x|  (fp64 accumulation).
  * bwd: dh = gloss[0] * weight * sign(recon-x) * recon*(1-recon) / n */

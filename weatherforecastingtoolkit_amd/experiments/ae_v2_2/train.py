@@ -9,8 +9,9 @@ Step order (reference training_step :126-159):
   G: Loss(optimizer_idx=0) = L1 [+ d_weight * -mean(D(pred)) once global_step >= disc_start]
      -> backward (discriminator frozen) -> clip-by-norm 1.0 -> AdamW -> cosine-warmup step
   D (global_step >= disc_start): hinge(D(inp), D(pred.detach())) -> backward -> clip -> AdamW -> step
-LPIPS (perceptual_weight > 0) needs VGG weights from the network and is not built; the shipped config
-sets perceptual_weight 0.0.
+LPIPS (lpips.perceptual_weight > 0, reference :56-60) runs on csrc/lpips.hip with weights the user supplies:
+--lpips-vgg PATH (a torchvision VGG16 state dict) --lpips-lin PATH (the LPIPS `vgg.pth` linear layers); nothing is
+fetched.  The shipped config sets perceptual_weight 0.0.
 """
 from __future__ import annotations
 
@@ -32,6 +33,7 @@ from ...nn import flush_bn_counters
 from ...pipeline import helpers
 from ...pipeline.datasets.sevire.sevir import SEVIRFrameLoader
 from ...pipeline.models.ae_64x8x8_lin import PosAwareAE_TF
+from ...pipeline.models.autoencoderkl.losses import LPIPS
 from .._gan import GanLoss, frozen
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,15 +55,31 @@ CARRIED_KEYS = {
 
 
 
+def add_lpips_arguments(ap):
+    ap.add_argument("--lpips-vgg", default=None, metavar="PATH",
+                    help="torchvision VGG16 state dict (features.N.weight / bias) for lpips.perceptual_weight > 0")
+    ap.add_argument("--lpips-lin", default=None, metavar="PATH", help="LPIPS linear layers (vgg.pth: linK.model.1.weight)")
+
+
+def lpips_from_arguments(args):
+    """the LPIPS module of --lpips-vgg / --lpips-lin, or None without them"""
+    if (args.lpips_vgg is None) != (args.lpips_lin is None):
+        raise WfaeError("--lpips-vgg and --lpips-lin go together")
+    return None if args.lpips_vgg is None else LPIPS.from_files(args.lpips_vgg, args.lpips_lin)
+
+
 class Loss(GanLoss):
     """reference experiments/ae_v2_2/train.py:29-95"""
 
     def __init__(self, disc_start, disc_num_layers=3, disc_in_channels=1, disc_weight=1.0, use_actnorm=False,
-                 perceptual_weight=1.0, recon_weight=1.0):
+                 perceptual_weight=1.0, recon_weight=1.0, *, lpips=None):
         super().__init__(disc_start, disc_num_layers, disc_in_channels, disc_weight, use_actnorm)
-        if perceptual_weight > 0:
-            raise WfaeError("Loss: perceptual_weight > 0 needs LPIPS (VGG16 weights fetched from the network); "
-                            "not built — every shipped config sets lpips.perceptual_weight=0.0")
+        if perceptual_weight > 0 and lpips is None:
+            raise WfaeError("Loss: perceptual_weight > 0 needs an LPIPS module (its VGG16 weights are not fetched from the "
+                            "network): pass lpips=LPIPS.from_files(...) / --lpips-vgg PATH --lpips-lin PATH, or set "
+                            "lpips.perceptual_weight=0.0 as every shipped config does")
+        if lpips is not None:
+            self.perceptual_loss = lpips.eval()                            # reference :41
         self.perceptual_weight, self.recon_weight = perceptual_weight, recon_weight
 
     def forward(self, inputs, reconstructions, optimizer_idx, last_layer, split, global_step):
@@ -70,6 +88,10 @@ class Loss(GanLoss):
             return d_loss, {f"{split}/disc_loss": d_loss.detach(), f"{split}/logits_real": logits_real.detach().mean(),
                             f"{split}/logits_fake": logits_fake.detach().mean()}
         rec_loss = Fn.l1_loss(reconstructions, inputs, self.recon_weight)
+        if self.perceptual_weight > 0:
+            # reference :56-60; the repeat(1, 3, 1, 1) of both images is the 1-channel form of the scaling kernel
+            perceptual = self.perceptual_loss(reconstructions, inputs.detach())
+            rec_loss = Fn.AddFn.apply(rec_loss, Fn.MeanFn.apply(perceptual, False, 1.0, float(self.perceptual_weight)))
         if global_step < self.disc_start:
             return rec_loss, {f"{split}/total_loss": rec_loss.detach(), f"{split}/rec_loss": rec_loss.detach(),
                               f"{split}/g_loss": 0.0, f"{split}/d_weight": 0.0}
@@ -82,14 +104,14 @@ class Model(tnn.Module):
     """reference Model (:98-214) minus Lightning: owns the autoencoder, the Loss, both optimisers and
     schedulers, and the manual-optimisation training step."""
 
-    def __init__(self, cfg, img_size=128):
+    def __init__(self, cfg, img_size=128, lpips=None):
         super().__init__()
         self.cfg = cfg
         self.autoencoder = PosAwareAE_TF(img_size=img_size)
         lp = cfg.lpips
         self.loss = Loss(lp.disc_start, disc_num_layers=lp.disc_num_layers, disc_in_channels=lp.disc_in_channels,
                          disc_weight=lp.disc_weight, use_actnorm=lp.use_actnorm,
-                         perceptual_weight=lp.perceptual_weight, recon_weight=lp.recon_weight)
+                         perceptual_weight=lp.perceptual_weight, recon_weight=lp.recon_weight, lpips=lpips)
         self.total_steps = cfg.trainer.total_train_steps
         self.accumulate_grad_batches = cfg.trainer.accumulate_grad_batches
         self.global_step = 0
@@ -206,6 +228,7 @@ def main(argv=None):
                     help="reference: torch.set_float32_matmul_precision('high') (train.py main).  'medium' = BASELINE "
                          "config 5's regime and MORE than torch's meaning of the word: bf16 MFMA operands AND bf16 activation "
                          "storage in HBM (the counterpart of bf16 autocast); WFAE_BF16_STORAGE=0 keeps the tensors fp32")
+    add_lpips_arguments(ap)
     args, unknown = ap.parse_known_args(argv)
     cfg = C.load(args.config, CARRIED_KEYS)
     cli = C.from_dotlist(unknown)
@@ -234,7 +257,7 @@ def main(argv=None):
 
     torch.manual_seed(0)
     Fn._seed_counter[0] = 0          # the counter-based dropout stream restarts with the run (restored on --resume)
-    model = Model(cfg, img_size=size).to(dev).train()
+    model = Model(cfg, img_size=size, lpips=lpips_from_arguments(args)).to(dev).train()
     Fn.set_wgrad_overlap(True)
     model.configure_optimizers()
 

@@ -29,7 +29,7 @@ from ...nn import flush_bn_counters
 from ...pipeline import helpers
 from ...pipeline.datasets.sevir.sevir import SEVIRLightningDataModule
 from ...pipeline.datasets.sevire.sevir import parse_presample, presample_line, resolve_presample
-from .train import CARRIED_KEYS, HERE, Model
+from .train import CARRIED_KEYS, HERE, Model, add_lpips_arguments, lpips_from_arguments
 
 
 def main(argv=None):
@@ -42,6 +42,7 @@ def main(argv=None):
     ap.add_argument("--presample", type=parse_presample, default="auto", metavar="auto|none|T,H,W",
                     help="with --data-dir: pool the events on the device as the loader converts them.  auto = (2, 3, 3) "
                          "when the config names sevirlr and the store holds raw 384x384x49 events, else none")
+    add_lpips_arguments(ap)
     args, unknown = ap.parse_known_args(argv)
     cfg = C.load(args.config, CARRIED_KEYS)
     cli = C.from_dotlist(unknown)
@@ -103,7 +104,7 @@ def main(argv=None):
 
     torch.manual_seed(0)
     Fn._seed_counter[0] = 0
-    model = Model(cfg, img_size=size).to(dev).train()
+    model = Model(cfg, img_size=size, lpips=lpips_from_arguments(args)).to(dev).train()
     Fn.set_wgrad_overlap(True)
     model.configure_optimizers()
 

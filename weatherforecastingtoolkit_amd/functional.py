@@ -1355,3 +1355,64 @@ def aekl_posterior(moments, noise=None):
     """-> (mean, logvar, std, sample): ops.aekl_posterior"""
     _aekl_no_grad("aekl_posterior", moments)
     return ops.aekl_posterior(_c(moments.detach()), None if noise is None else _c(noise))
+
+
+# ---- LPIPS perceptual loss (csrc/lpips.hip; reference pipeline/models/autoencoderkl/losses/lpips.py:47-60,107-129)
+LPIPS_SLICES = (2, 2, 3, 3, 3)   # 3x3 conv + ReLU layers per VGG16 slice; a 2 x 2 max-pool opens slices 2..5; a tap closes each
+
+
+class LpipsFn(Function):
+    """(N, 1, 1, 1) LPIPS distance of x to target, gradient to x only.  `st` (losses/lpips.py `LPIPS._state`) carries the
+    frozen operands: shift, scale, 13 packed forward weights `fwd`, 13 packed rotated / transposed weights `bwd`, biases,
+    input channel counts `cin`, 5 `lin` vectors and the conv `mode`.  x and target go through the VGG as one 2N batch.
+    Saved for backward: the five tap activations whole (the target half is the distance's second operand) and a copy of
+    the recon half of the other eight.  backward only reads them and allocates its results, so it may run any number
+    of times (autograd.grad(..., retain_graph=True) for the adaptive weight, then the real backward).  `sink`: a list
+    that receives the recon half of the 13 activations, or None."""
+
+    @staticmethod
+    def forward(ctx, x, target, st, sink):
+        x, target = _c(x), _c(target)
+        n, _, h, w = x.shape
+        z = torch.empty((2 * n, 3, h, w), dtype=torch.float32, device=x.device)
+        ops.lpips_prep_fwd(x, st.shift, st.scale, z[:n])
+        ops.lpips_prep_fwd(target, st.shift, st.scale, z[n:])
+        keep = ctx.needs_input_grad[0]
+        out = torch.zeros((n, 1, 1, 1), dtype=torch.float32, device=x.device)
+        saved, li, hcur = [], 0, z
+        for s, nconv in enumerate(LPIPS_SLICES):
+            if s:
+                hcur = ops.lpips_pool_fwd(hcur)
+            for j in range(nconv):
+                hcur = ops.lpips_conv3_fwd(hcur, st.fwd[li], st.bias[li], st.mode)
+                li += 1
+                tap = j == nconv - 1
+                if tap:
+                    ops.lpips_dist_fwd(hcur[:n], hcur[n:], st.lin[s], out)
+                if keep or sink is not None:
+                    saved.append(hcur if tap else hcur[:n].clone())
+        if sink is not None:
+            sink.extend(a[:n] for a in saved)
+        if keep:
+            ctx.save_for_backward(*saved)
+            ctx.st, ctx.cx = st, x.shape[1]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        saved, st = ctx.saved_tensors, ctx.st
+        g = _c(g).view(-1)
+        n = g.numel()
+        li, d = len(saved) - 1, None
+        for s in reversed(range(len(LPIPS_SLICES))):
+            a0, a1 = saved[li][:n], saved[li][n:]
+            if d is None:      # relu5_3: no pool follows, the distance gradient takes the ReLU mask itself
+                d = ops.lpips_dist_bwd(a0, a1, st.lin[s], g, relu=True)
+            else:
+                d = ops.lpips_pool_bwd(a0, d, ops.lpips_dist_bwd(a0, a1, st.lin[s], g))
+            for j in reversed(range(LPIPS_SLICES[s])):
+                # d: gradient of layer li's pre-activation -> of the pre-activation of the layer that feeds it (the first
+                # layer of a slice is fed by the pool / the scaling layer: no mask)
+                d = ops.lpips_conv3_bwd_data(d, st.bwd[li], st.cin[li], saved[li - 1][:n] if j else None, st.mode)
+                li -= 1
+        return ops.lpips_prep_bwd(d, st.scale, ctx.cx), None, None, None

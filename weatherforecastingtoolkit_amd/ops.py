@@ -1770,6 +1770,133 @@ def aekl_posterior(moments, noise=None):
     return mean, logvar, std, sample
 
 
+# ---- LPIPS perceptual loss (include/wfae.h "LPIPS perceptual loss"; csrc/lpips.hip).  The conv shares the packed weights
+# and the modes of the AutoencoderKL 3x3 kernel: pack with aekl_conv3_pack.
+def _lpips_packed(what, packed, cout, cin, mode):
+    want = _lib.load().wfae_aekl_conv3_pack_bytes(cout, cin, mode)
+    if want == 0 or packed.dtype != torch.uint8 or packed.numel() != want or not packed.is_cuda:
+        raise _lib.WfaeError(f"{what}: packed weights do not belong to Cout={cout} Cin={cin} mode={mode}")
+    return want
+
+
+def lpips_conv3_fwd(x, packed, bias, mode=None):
+    """relu(conv3x3(x, stride 1, pad 1) + bias); packed = aekl_conv3_pack(w (Cout, Cin, 3, 3), mode)"""
+    mode = aekl_mode() if mode is None else mode
+    _chk(x, bias)
+    if x.dim() != 4 or bias is None or bias.dim() != 1:
+        raise _lib.WfaeError("lpips_conv3_fwd: expected x (N, C, H, W) and bias (Cout,)")
+    n, cin, h, wd = x.shape
+    cout = bias.shape[0]
+    want = _lpips_packed("lpips_conv3_fwd", packed, cout, cin, mode)
+    y = torch.empty((n, cout, h, wd), dtype=torch.float32, device=x.device)
+    _call("wfae_lpips_conv3_fwd", 2 * 9 * n * h * wd * cin * cout, 4 * (x.numel() + y.numel()) + want, _p(x),
+          packed.data_ptr(), _p(bias), _p(y), mode, n, cin, cout, h, wd, _stream(),
+          label=f"wfae_lpips_conv3_fwd {cin}->{cout} {h}x{wd}", peak=_aekl_peak(mode))
+    return y
+
+
+def lpips_conv3_bwd_data(dy, packed_t, cin, a_prev=None, mode=None):
+    """dx (N, cin, H, W) = conv3x3(dy, rotated / transposed weights) * (a_prev > 0);
+    packed_t = aekl_conv3_pack(w.flip(2, 3).transpose(0, 1), mode)"""
+    mode = aekl_mode() if mode is None else mode
+    _chk(dy, a_prev)
+    if dy.dim() != 4:
+        raise _lib.WfaeError(f"lpips_conv3_bwd_data: expected dy (N, C, H, W), got {tuple(dy.shape)}")
+    n, cout, h, wd = dy.shape
+    want = _lpips_packed("lpips_conv3_bwd_data", packed_t, cin, cout, mode)
+    if a_prev is not None and tuple(a_prev.shape) != (n, cin, h, wd):
+        raise _lib.WfaeError(f"lpips_conv3_bwd_data: a_prev {tuple(a_prev.shape)}, expected {(n, cin, h, wd)}")
+    dx = torch.empty((n, cin, h, wd), dtype=torch.float32, device=dy.device)
+    _call("wfae_lpips_conv3_bwd_data", 2 * 9 * n * h * wd * cin * cout,
+          4 * (dy.numel() + dx.numel() * (2 if a_prev is not None else 1)) + want, _p(dy), packed_t.data_ptr(), _p(a_prev),
+          _p(dx), mode, n, cin, cout, h, wd, _stream(), label=f"wfae_lpips_conv3_bwd_data {cout}->{cin} {h}x{wd}",
+          peak=_aekl_peak(mode))
+    return dx
+
+
+def lpips_pool_fwd(x):
+    """2 x 2 stride-2 max-pool, floor on odd sizes"""
+    _chk(x)
+    if x.dim() != 4 or x.shape[2] < 2 or x.shape[3] < 2:
+        raise _lib.WfaeError(f"lpips_pool_fwd: expected (N, C, H >= 2, W >= 2), got {tuple(x.shape)}")
+    n, c, h, wd = x.shape
+    y = torch.empty((n, c, h // 2, wd // 2), dtype=torch.float32, device=x.device)
+    _call("wfae_lpips_pool_fwd", 0, 4 * (x.numel() + y.numel()), _p(x), _p(y), n, c, h, wd, _stream())
+    return y
+
+
+def lpips_pool_bwd(a, dy, add=None):
+    """gradient of the pre-activation of the pool's input a (post-ReLU): torch's max-pool routing of dy, + add, * (a > 0)"""
+    _chk(a, dy, add)
+    if a.dim() != 4 or a.shape[2] < 2 or a.shape[3] < 2:
+        raise _lib.WfaeError(f"lpips_pool_bwd: expected a (N, C, H >= 2, W >= 2), got {tuple(a.shape)}")
+    n, c, h, wd = a.shape
+    if tuple(dy.shape) != (n, c, h // 2, wd // 2) or (add is not None and add.shape != a.shape):
+        raise _lib.WfaeError(f"lpips_pool_bwd: dy {tuple(dy.shape)} / add do not belong to a {tuple(a.shape)}")
+    dpre = torch.empty_like(a)
+    _call("wfae_lpips_pool_bwd", 0, 4 * (a.numel() * (3 if add is not None else 2) + dy.numel()), _p(a), _p(dy), _p(add),
+          _p(dpre), n, c, h, wd, _stream())
+    return dpre
+
+
+def _lpips_dist_args(what, a0, a1, lin):
+    _chk(a0, a1, lin)
+    if a0.dim() != 4 or a1.shape != a0.shape or lin.numel() != a0.shape[1]:
+        raise _lib.WfaeError(f"{what}: a0 {tuple(a0.shape)}, a1 {tuple(a1.shape)}, lin {tuple(lin.shape)}")
+    if a0.shape[1] not in (64, 128, 256, 512):
+        raise _lib.WfaeError(f"{what}: {a0.shape[1]} channels, served are 64, 128, 256 and 512")
+    return a0.shape[0], a0.shape[1], a0.shape[2] * a0.shape[3]
+
+
+def lpips_dist_fwd(a0, a1, lin, out):
+    """out (N) += mean over pixels of sum_c lin[c] (a0 / (||a0|| + 1e-10) - a1 / (||a1|| + 1e-10))^2, in place"""
+    n, c, hw = _lpips_dist_args("lpips_dist_fwd", a0, a1, lin)
+    _chk(out)
+    if out.numel() != n:
+        raise _lib.WfaeError(f"lpips_dist_fwd: out {tuple(out.shape)}, expected {n} values")
+    ws = workspace(_lib.load().wfae_lpips_dist_ws_bytes(n, hw))
+    _call("wfae_lpips_dist_fwd", 0, 8 * a0.numel(), _p(a0), _p(a1), _p(lin), _p(out), n, c, hw, ws.data_ptr(), ws.numel(),
+          _stream())
+    return out
+
+
+def lpips_dist_bwd(a0, a1, lin, g, relu=False):
+    """g[n] * d(the layer's term of sample n) / d a0; relu: times (a0 > 0).  Finite at an all-zero pixel of a0 (wfae.h)."""
+    n, c, hw = _lpips_dist_args("lpips_dist_bwd", a0, a1, lin)
+    _chk(g)
+    if g.numel() != n:
+        raise _lib.WfaeError(f"lpips_dist_bwd: g {tuple(g.shape)}, expected {n} values")
+    da0 = torch.empty(a0.shape, dtype=torch.float32, device=a0.device)
+    _call("wfae_lpips_dist_bwd", 0, 12 * a0.numel(), _p(a0), _p(a1), _p(lin), _p(g), _p(da0), n, c, hw, int(bool(relu)),
+          _stream())
+    return da0
+
+
+def lpips_prep_fwd(x, shift, scale, out=None):
+    """(x - shift[c]) / scale[c] into 3 channels from a 1- or 3-channel x (N, Cx, H, W); `out`: where to write (N, 3, H, W)"""
+    _chk(x, shift, scale, out)
+    if x.dim() != 4 or x.shape[1] not in (1, 3) or shift.numel() != 3 or scale.numel() != 3:
+        raise _lib.WfaeError(f"lpips_prep_fwd: expected x (N, 1 or 3, H, W) and 3 shifts / scales, got {tuple(x.shape)}")
+    n, cx, h, wd = x.shape
+    if out is None:
+        out = torch.empty((n, 3, h, wd), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, 3, h, wd):
+        raise _lib.WfaeError(f"lpips_prep_fwd: out {tuple(out.shape)}, expected {(n, 3, h, wd)}")
+    _call("wfae_lpips_prep_fwd", 0, 4 * (x.numel() + out.numel()), _p(x), _p(shift), _p(scale), _p(out), n, cx, h * wd, _stream())
+    return out
+
+
+def lpips_prep_bwd(dy, scale, cx):
+    """dx (N, cx, H, W) of lpips_prep_fwd"""
+    _chk(dy, scale)
+    if dy.dim() != 4 or dy.shape[1] != 3 or cx not in (1, 3) or scale.numel() != 3:
+        raise _lib.WfaeError(f"lpips_prep_bwd: expected dy (N, 3, H, W), cx 1 or 3, got {tuple(dy.shape)}, cx={cx}")
+    n, _, h, wd = dy.shape
+    dx = torch.empty((n, cx, h, wd), dtype=torch.float32, device=dy.device)
+    _call("wfae_lpips_prep_bwd", 0, 4 * (dy.numel() + dx.numel()), _p(dy), _p(scale), _p(dx), n, cx, h * wd, _stream())
+    return dx
+
+
 def ssim_fwd(x, y, clamp01=False):
     _chk(x, y)
     nb = x.shape[0] * x.shape[1]

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 from ..... import functional as Fn
+from .lpips import LPIPS  # noqa: F401  (the reference imports it from here: experiments/ae_v2_2/train.py:10)
 
 
 def adopt_weight(weight, global_step, threshold=0, value=0.0):
