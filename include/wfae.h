@@ -88,6 +88,14 @@ int wfae_get_matmul_precision(void);
 int wfae_set_split_gemm(int on);
 int wfae_get_split_gemm(void);
 
+/* The narrowing 1x1 products of the C >= 512 Bottlenecks (wfae_conv1x1_fwd / _fwd_stats / _fwd_bnact without bias and
+ * residual, and wfae_conv1x1_bwd_data, at (Cout, Cin) resp. (Cin, Cout) = (128, 512) or (256, 1024), HW % 8 == 0, 16-byte
+ * aligned tensors, fp32 precision with the split GEMMs on) run on csrc/c1n.hip: both operands are split into their three
+ * bf16 planes once, on their way into LDS.  On by default (environment WFAE_C1N=0 turns it off at load); 0 keeps these shapes on the in-register split of the generic
+ * GEMM kernel (the A/B switch of tools/kbench.py and tests/test_c1n_gpu.py).  Process-wide; read at launch. */
+int wfae_set_c1n(int on);
+int wfae_get_c1n(void);
+
 /* ---- 1x1 convolution as an fp32-MFMA GEMM on NCHW ------------------------
  * replaces nn.Conv2d(C, C/4, 1) / (C/4, C, 1) in Bottleneck
  * (pipeline/models/ae_64x8x8_lin.py:15,19) and the latent projections

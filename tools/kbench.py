@@ -148,6 +148,30 @@ def main():
                     acc(key + ("_c1r" if on else "_old"), ms, mult)
             ops.set_c1r(True)
             del x, t2, w1, w3
+    if "c1n" in only:
+        # csrc/c1n.hip (operands split once on their way into LDS) against gemm.hip's in-register split, the narrowing products of
+        # the C >= 512 stages in the forms the step launches them; two passes, old and new interleaved: the spread of a kernel
+        # between the passes is the noise its gain is read against
+        for rep in range(-1, 2):     # pass -1 warms the clocks up and is not reported
+            for c, h in [(512, S // 4), (1024, S // 8), (1024, S // 16)]:
+                mult = 4 if h == S // 16 else 8
+                mid = c // 4
+                n = B * h * h
+                x = rnd(B, c, h, h)
+                w1, w3 = rnd(mid, c, 1, 1) * c ** -0.5, rnd(c, mid, 1, 1) * mid ** -0.5
+                g, b_, rm, rv = torch.ones(c, device=dev), torch.zeros(c, device=dev), torch.zeros(c, device=dev), torch.ones(c, device=dev)
+                st = ops.bn_stats_train(x, g, b_, rm, rv)
+                fl, by1 = 2 * n * c * mid, 4 * n * (c + mid)
+                for tag, fn, key in [(f"fwd  {c}->{mid} bnact+stats", lambda: ops.conv1x1_fwd_bnact(x, st, w1, stats=True), "fwd1"),
+                                     (f"dgrad {c}->{mid} (da3)", lambda: ops.conv1x1_bwd_data(x, w3), "dgrad3")]:
+                    for on in (False, True):
+                        ops.set_c1n(on)
+                        ms = timeit(fn, R)
+                        if rep >= 0:
+                            report(f"c1n @{h} {tag} {'c1n' if on else 'gemm.hip'} pass{rep}", ms, fl, by1)
+                            acc(f"c1n_{key}_{'new' if on else 'old'}_pass{rep}", ms, mult)
+                ops.set_c1n(True)
+                del x, w1, w3
     if "bnseq" in only:
         # first BatchNorm of a Bottleneck, backward: data gradient of the C -> C/4 convolution + BatchNorm/GELU backward (+ residual
         # gradient), with the reduce pass separate or in the c1r epilogue (ops.set_c1r_bnred)

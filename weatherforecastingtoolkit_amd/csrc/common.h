@@ -263,6 +263,13 @@ int split_gemm(int kind, int planes, const unsigned short* A, const unsigned sho
                long c_split, hipStream_t st, const char* what);
 int wino_weights_t(int variant, const float* dU, float* dw, int Clo, int Chi, int beta, hipStream_t st);     // G^T dU G
 
+// narrowing 1x1 products of the C >= 512 Bottlenecks on the split GEMM's loop with fp32 operands split on their way into LDS
+// (c1n.hip): y = A f(x), A = w (M, K) row-major or, transposed, A[m][k] = w[k][m]; f = gelu(x scale[k] + shift[k]) when scale
+// is given; stat_part: the BatchNorm sums of y as StatRows (*stat_rows set).  1: launched; 0: shape not served (nothing
+// written, the caller keeps its own kernel); < 0: error
+int c1n_launch(const float* w, bool transposed, const float* x, const float* scale, const float* shift, float* y, int NB, int K, int M,
+               int HW, double* stat_part, int64_t stat_capacity, int* stat_rows, hipStream_t st, const char* what);
+
 // out = (beta ? out : 0) + sum over `splits` partial slabs of MN floats (+ bias_n[i % N]); fixed order.
 int slab_reduce(const float* slab, float* out, const float* bias_n, long MN, int N, int splits, int beta,
                 hipStream_t st, int transpose_m = 0);

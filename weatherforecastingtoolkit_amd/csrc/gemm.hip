@@ -1437,6 +1437,14 @@ static int conv1x1_fwd_impl(const T* x, const float* bn_scale, const float* bn_s
   WFAE_REQUIRE(x && w && y, WFAE_ERR_NULL_POINTER, "conv1x1_fwd: null pointer");
   WFAE_REQUIRE(NB > 0 && Cin > 0 && Cout > 0 && HW > 0, WFAE_ERR_BAD_SHAPE, "conv1x1_fwd: bad shape");
   WFAE_REQUIRE((int64_t)NB * HW < (1ll << 31), WFAE_ERR_BAD_SHAPE, "conv1x1_fwd: NB*HW too large");
+  if constexpr (std::is_same<T, float>::value) {
+    // the narrowing products of the C >= 512 Bottlenecks: operands activated and split once on their way into LDS (c1n.hip)
+    if (!bias && !res) {
+      const int rc = wfae::c1n_launch(w, false, x, bn_scale, bn_shift, y, NB, Cin, Cout, HW, stat_rows ? stat_part : nullptr,
+                                      stat_capacity, stat_rows, (hipStream_t)stream, bn_scale ? "conv1x1_fwd_bnact" : "conv1x1_fwd");
+      if (rc != 0) return rc < 0 ? rc : WFAE_OK;
+    }
+  }
   GemmP p = {};
   p.A = w; p.B = x; p.C = y; p.bias = bias; p.res = res;
   p.b_scale = bn_scale; p.b_shift = bn_shift;
@@ -1584,6 +1592,12 @@ static int conv1x1_bwd_data_impl(const T* dy, const float* w, T* dx, int NB, int
   WFAE_REQUIRE(dy && w && dx, WFAE_ERR_NULL_POINTER, "conv1x1_bwd_data: null pointer");
   WFAE_REQUIRE(NB > 0 && Cin > 0 && Cout > 0 && HW > 0, WFAE_ERR_BAD_SHAPE, "conv1x1_bwd_data: bad shape");
   WFAE_REQUIRE((int64_t)NB * HW < (1ll << 31), WFAE_ERR_BAD_SHAPE, "conv1x1_bwd_data: NB*HW too large");
+  if constexpr (std::is_same<T, float>::value) {
+    // the C -> C/4 data gradients of the C >= 512 Bottlenecks (c1n.hip): A[m = ci][k = co] = w[co * Cin + ci]
+    const int rc = wfae::c1n_launch(w, true, dy, nullptr, nullptr, dx, NB, Cout, Cin, HW, nullptr, 0, nullptr, (hipStream_t)stream,
+                                    "conv1x1_bwd_data");
+    if (rc != 0) return rc < 0 ? rc : WFAE_OK;
+  }
   GemmP p = {};
   p.A = w; p.B = dy; p.C = dx;
   p.M = Cin; p.N = NB * HW; p.K = Cout; p.k_per_split = cdiv(Cout, BK) * BK;

@@ -342,6 +342,17 @@ def c1r_bndx(w, dt, x, gamma, st, res=None, training=True):
     return dx
 
 
+# csrc/c1n.hip: the narrowing products of the C >= 512 stages ((M, K) = (128, 512), (256, 1024)), routed inside the library
+# from wfae_conv1x1_fwd / _fwd_stats / _fwd_bnact (no bias, no residual) and wfae_conv1x1_bwd_data
+def set_c1n(on):
+    """A/B switch: those products on csrc/c1n.hip (operands split once on their way into LDS) or on gemm.hip's in-register split"""
+    _lib.call("wfae_set_c1n", int(bool(on)))
+
+
+def c1n_enabled():
+    return bool(_lib.load().wfae_get_c1n())
+
+
 # csrc/c1rb.hip: the same register-direct product on bf16-stored tensors ('medium'): every Bottleneck stage with HW % 128 == 0
 _C1RB = True   # A/B through set_c1rb()
 
