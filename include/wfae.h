@@ -878,6 +878,38 @@ int wfae_vil_augment_u8_to_f32(const uint8_t* src, const float* xf, float* dst, 
 int wfae_vil_pool_u8_to_f32(const uint8_t* src, const float* xf /* may be NULL */, float* dst, int NB, int H, int W, int T,
                             int ft, int fh, int fw, int mode, float scale, float offset, wfae_stream_t stream);
 
+/* ---- 3x3 stride-2 padding-1 convolution family of the conv + GAN latent model (csrc/c3s2.hip; reference
+ * experiments/v1_experiments/pretrained_ae_conv_disc/train.py:140-188 `Encoder`, `Decoder`).  Added within ABI version
+ * 103; nothing changed.
+ * One weight layout w (Clo, Chi, 3, 3): Conv2d(Chi -> Clo).weight, and ConvTranspose2d(Clo -> Chi).weight.  "hi" is the
+ * larger plane (N, Chi, Hhi, Whi), "lo" the smaller (N, Clo, Hlo, Wlo); Hlo = (Hhi - 1) / 2 + 1 (so Hhi = 2 Hlo - 1 +
+ * output_padding, output_padding 0 or 1), likewise W.  transposed = 0: the module is Conv2d (x is hi, y is lo, bias Clo);
+ * transposed = 1: ConvTranspose2d (x is lo, y is hi, bias Chi).  act: 0 = none, 1 = SiLU.
+ *   wfae_c3s2_fwd:        t = conv(x) + bias (bias may be NULL), y = act(t); t may be NULL (nothing saved).
+ *   wfae_c3s2_bwd_data:   dx = conv_data_gradient(da act'(t)); t is read only when act = 1.
+ *   wfae_c3s2_bwd_weight: dw (and dbias unless NULL) of dt = da act'(t) against the module input x, the bias gradient from
+ *                         extra workgroups of the same launch; accumulate: add to dw / dbias instead of overwriting.
+ * dt is formed inside the kernels that read da.  Tap (ky, kx) is DEAD when no lo position reads a real hi pixel through it
+ * (wfae_c3s2_live_taps: bit ky * 3 + kx set = live; at 2x2 -> 1x1 only ky, kx in {1, 2} are live): dead weights never enter
+ * the arithmetic, dead gradients are written as exact zeros, or left untouched when accumulating.  Dead weights ARE fetched:
+ * the nine taps of a (cl, ch) pair are 36 contiguous bytes, so they share their 16-byte accesses and 128-byte lines with
+ * live ones and are zeroed in registers; skipping them saves arithmetic, not memory traffic.
+ * Reductions are split over workgroups and finished from the workspace in a fixed order: no atomics, bitwise repeatable.
+ * ws: wfae_c3s2_workspace_bytes(op, ...) bytes, op 0 = fwd, 1 = bwd_data, 2 = bwd_weight (0 for shapes that are refused).
+ * Errors, all before any launch: null pointers WFAE_ERR_NULL_POINTER; a size < 1, an unknown act or a tensor of 2^31
+ * elements WFAE_ERR_BAD_SHAPE; Hlo / Hhi (Wlo / Whi) that do not belong together, or more than 65535 tiles of 8 lo rows
+ * (N Hlo Wlo > 524280: one grid dimension counts them), WFAE_ERR_UNSUPPORTED; a short workspace WFAE_ERR_WORKSPACE. */
+int wfae_c3s2_live_taps(int Hhi, int Whi, int Hlo, int Wlo);
+size_t wfae_c3s2_workspace_bytes(int op, int transposed, int N, int Chi, int Clo, int Hhi, int Whi, int Hlo, int Wlo);
+int wfae_c3s2_fwd(const float* x, const float* w, const float* bias /* may be NULL */, float* y, float* t /* may be NULL */,
+                  int transposed, int act, int N, int Chi, int Clo, int Hhi, int Whi, int Hlo, int Wlo, void* ws,
+                  size_t ws_bytes, wfae_stream_t stream);
+int wfae_c3s2_bwd_data(const float* da, const float* t, const float* w, float* dx, int transposed, int act, int N, int Chi,
+                       int Clo, int Hhi, int Whi, int Hlo, int Wlo, void* ws, size_t ws_bytes, wfae_stream_t stream);
+int wfae_c3s2_bwd_weight(const float* da, const float* t, const float* x, float* dw, float* dbias /* may be NULL */,
+                         int transposed, int act, int accumulate, int N, int Chi, int Clo, int Hhi, int Whi, int Hlo, int Wlo,
+                         void* ws, size_t ws_bytes, wfae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

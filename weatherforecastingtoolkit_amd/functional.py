@@ -1290,6 +1290,44 @@ def conv_layernorm_act(x, w, bias, gamma, beta, kind, slope=0.01):
     return ConvLayerNormActFn.apply(x, w, bias, gamma, beta, int(kind), float(slope))
 
 
+class Conv3x3s2ActFn(Function):
+    """one unit of the conv + GAN latent model (reference v1_experiments/pretrained_ae_conv_disc/train.py:144-180):
+    Conv2d(3x3, stride 2, padding 1) or, transposed, ConvTranspose2d(3x3, stride 2, padding 1, output_padding), with bias
+    and, with act, SiLU — one entry point forward, one for the data gradient, one for the weight and bias gradients
+    (csrc/c3s2.hip).  w is (Clo, Chi, 3, 3) for both module types.  Saved for backward: x and the pre-activation t, which
+    is a few KiB next to the MiB of weights a recomputation would stream again; SiLU'(t) is applied inside the backward
+    kernels.  The data gradient is formed only when x requires one."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, transposed, act, output_padding):
+        x = _c(x)
+        y, t = ops.c3s2_fwd(x, w, bias, transposed, act, output_padding, save_t=act)
+        ctx.save_for_backward(x, w, t)
+        ctx.bias, ctx.transposed, ctx.act = bias, transposed, act
+        return y
+
+    @staticmethod
+    def backward(ctx, da):
+        x, w, t = ctx.saved_tensors
+        da = _c(da)
+        dw = db = dx = None
+        need_w, need_b = ctx.needs_input_grad[1], ctx.bias is not None and ctx.needs_input_grad[2]
+        if need_w or need_b:
+            # one launch gives both; a frozen weight next to a trainable bias gets a throw-away buffer
+            dw = grad_buffer(w) if need_w else torch.empty_like(w)
+            db = grad_buffer(ctx.bias) if need_b else None
+            ops.c3s2_bwd_weight(da, t, x, dw, db, ctx.transposed, ctx.act)
+            if not need_w:
+                dw = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.c3s2_bwd_data(da, t, w, x.shape, ctx.transposed, ctx.act)
+        return dx, dw, db, None, None, None
+
+
+def conv3x3s2_act(x, w, bias=None, transposed=False, act=True, output_padding=1):
+    return Conv3x3s2ActFn.apply(x, w, bias, bool(transposed), bool(act), output_padding)
+
+
 class HuberLossFn(Function):
     """nn.HuberLoss(delta) with mean reduction (reference pretrained_ae_convae_sevir/train.py:155)"""
 

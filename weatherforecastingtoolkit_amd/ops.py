@@ -1649,6 +1649,96 @@ def huber_bwd(pred, target, gloss, delta=1.0):
     return d
 
 
+# ---- 3x3 stride-2 padding-1 convolution family of the conv + GAN latent model (include/wfae.h "3x3 stride-2"; csrc/c3s2.hip)
+# w (Clo, Chi, 3, 3) is Conv2d(Chi -> Clo).weight and ConvTranspose2d(Clo -> Chi).weight; transposed names the module type.
+def c3s2_live_taps(hhi, whi, hlo=None, wlo=None):
+    """-> the 3 x 3 nested list of booleans: tap (ky, kx) is live iff some lo position (oy, ox) reads a real hi pixel
+    through it, 0 <= 2 oy - 1 + ky < Hhi and likewise in x.  Pure host arithmetic (the library's rule is
+    wfae_c3s2_live_taps)."""
+    hlo = (hhi - 1) // 2 + 1 if hlo is None else hlo
+    wlo = (whi - 1) // 2 + 1 if wlo is None else wlo
+
+    def axis(k, hi, lo):
+        # o = 0 reaches k = 1, 2 (source k - 1); o = 1 reaches k = 0 (source 1)
+        return (k >= 1 and k - 1 < hi) or (k == 0 and lo >= 2 and hi >= 2)
+    return [[axis(ky, hhi, hlo) and axis(kx, whi, wlo) for kx in range(3)] for ky in range(3)]
+
+
+def _c3s2_geo(what, w, transposed, x_shape, output_padding=1):
+    """-> (N, Chi, Clo, Hhi, Whi, Hlo, Wlo) from the module input's shape"""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise _lib.WfaeError(f"{what}: weight shape {tuple(w.shape)}, expected (Clo, Chi, 3, 3)")
+    clo, chi = w.shape[0], w.shape[1]
+    if len(x_shape) != 4 or x_shape[1] != (clo if transposed else chi):
+        raise _lib.WfaeError(f"{what}: input {tuple(x_shape)} against {'ConvTranspose2d' if transposed else 'Conv2d'} "
+                             f"weight {tuple(w.shape)}")
+    n, _, h, wd = x_shape
+    if transposed:
+        oph, opw = output_padding if isinstance(output_padding, (tuple, list)) else (output_padding, output_padding)
+        if oph not in (0, 1) or opw not in (0, 1):
+            raise _lib.WfaeError(f"{what}: output_padding {output_padding!r}, a stride-2 transpose takes 0 or 1 (per axis)")
+        return n, chi, clo, 2 * h - 1 + oph, 2 * wd - 1 + opw, h, wd
+    return n, chi, clo, h, wd, (h - 1) // 2 + 1, (wd - 1) // 2 + 1
+
+
+def _c3s2_ws(op, transposed, geo):
+    return workspace(_lib.load().wfae_c3s2_workspace_bytes(op, int(transposed), *geo))
+
+
+def c3s2_fwd(x, w, bias=None, transposed=False, act=True, output_padding=1, save_t=True):
+    """-> (y, t): t = conv(x) + bias (pre-activation, None unless save_t), y = SiLU(t) if act else t.  Conv2d 3x3 s2 p1, or
+    with transposed ConvTranspose2d 3x3 s2 p1 with output_padding (an int, or one per axis)"""
+    geo = _c3s2_geo("c3s2_fwd", w, transposed, tuple(x.shape), output_padding)
+    _chk(x, w, bias)
+    n, chi, clo, hhi, whi, hlo, wlo = geo
+    y = torch.empty((n, chi, hhi, whi) if transposed else (n, clo, hlo, wlo), dtype=torch.float32, device=x.device)
+    t = torch.empty_like(y) if save_t else None
+    ws = _c3s2_ws(0, transposed, geo)
+    live = sum(map(sum, c3s2_live_taps(hhi, whi, hlo, wlo)))
+    _call("wfae_c3s2_fwd", 2 * n * hlo * wlo * clo * chi * 9, 4 * (w.numel() * live // 9 + x.numel() + 2 * y.numel()),
+          _p(x), _p(w), _p(bias), _p(y), _p(t), int(transposed), int(act), *geo, ws.data_ptr(), ws.numel(), _stream())
+    return y, t
+
+
+def _c3s2_geo_pair(what, w, hi_shape, lo_shape):
+    """geometry from the shapes of the hi and the lo tensor; the library checks that the planes belong together"""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise _lib.WfaeError(f"{what}: weight shape {tuple(w.shape)}, expected (Clo, Chi, 3, 3)")
+    clo, chi = w.shape[0], w.shape[1]
+    if len(hi_shape) != 4 or len(lo_shape) != 4 or hi_shape[0] != lo_shape[0] or hi_shape[1] != chi or lo_shape[1] != clo:
+        raise _lib.WfaeError(f"{what}: tensors {tuple(hi_shape)} (hi) / {tuple(lo_shape)} (lo) against weight {tuple(w.shape)}")
+    return hi_shape[0], chi, clo, hi_shape[2], hi_shape[3], lo_shape[2], lo_shape[3]
+
+
+def c3s2_bwd_data(da, t, w, x_shape, transposed=False, act=True):
+    """-> dx of shape x_shape (the module input's): the data gradient for dt = da SiLU'(t) (da itself without act)"""
+    _chk(da, t, w)
+    x_shape = tuple(x_shape)
+    geo = _c3s2_geo_pair("c3s2_bwd_data", w, da.shape if transposed else x_shape, x_shape if transposed else da.shape)
+    n, chi, clo, hhi, whi, hlo, wlo = geo
+    dx = torch.empty(x_shape, dtype=torch.float32, device=da.device)
+    ws = _c3s2_ws(1, transposed, geo)
+    live = sum(map(sum, c3s2_live_taps(hhi, whi, hlo, wlo)))
+    _call("wfae_c3s2_bwd_data", 2 * n * hlo * wlo * clo * chi * 9, 4 * (w.numel() * live // 9 + 2 * da.numel() + dx.numel()),
+          _p(da), _p(t), _p(w), _p(dx), int(transposed), int(act), *geo, ws.data_ptr(), ws.numel(), _stream())
+    return dx
+
+
+def c3s2_bwd_weight(da, t, x, dw, dbias=None, transposed=False, act=True, accumulate=False):
+    """dw (Clo, Chi, 3, 3) and dbias of dt = da SiLU'(t) against the module input x, one call; dead taps of dw become exact
+    zeros, or stay as they are when accumulating"""
+    _chk(da, t, x, dw, dbias)
+    hi, lo = (da, x) if transposed else (x, da)
+    geo = _c3s2_geo_pair("c3s2_bwd_weight", dw, hi.shape, lo.shape)
+    n, chi, clo, hhi, whi, hlo, wlo = geo
+    ws = _c3s2_ws(2, transposed, geo)
+    live = sum(map(sum, c3s2_live_taps(hhi, whi, hlo, wlo)))
+    _call("wfae_c3s2_bwd_weight", 2 * n * hlo * wlo * clo * chi * 9, 4 * (dw.numel() * live // 9 + 2 * da.numel() + x.numel()),
+          _p(da), _p(t), _p(x), _p(dw), _p(dbias), int(transposed), int(act), int(accumulate), *geo, ws.data_ptr(),
+          ws.numel(), _stream())
+    return dw
+
+
 # ---- frozen AutoencoderKL latent provider (include/wfae.h "frozen AutoencoderKL"; csrc/aekl.hip), forward only
 AEKL_KINDS = {"conv": 0, "down": 1, "up": 2}
 AEKL_MODES = {"bf16": 1, "split3": 3, "fp32": 4}
