@@ -910,6 +910,54 @@ int wfae_c3s2_bwd_weight(const float* da, const float* t, const float* x, float*
                          int transposed, int act, int accumulate, int N, int Chi, int Clo, int Hhi, int Whi, int Hlo, int Wlo,
                          void* ws, size_t ws_bytes, wfae_stream_t stream);
 
+/* ---- conv + attention latent autoencoder (csrc/convattn.hip; reference
+ * experiments/v1_experiments/pretrained_ae_convattn_ae_sevir/train.py:58-161 `ConvAttnModel`).  Added within ABI version
+ * 103; nothing changed: wfae_mha_* (S <= 64) and wfae_sq_attn_* (L <= 64) above keep their kernels and their bits.
+ *
+ * attn: multi-head attention with separate query and key / value lengths, 1 <= Sq, Skv <= WFAE_ATTN_MAX_S, D = 16 (other
+ *   head sizes: WFAE_ERR_UNSUPPORTED), any H; E = H * D.  Batch-first rows: query row n * Sq + i, key / value row
+ *   n * Skv + j.  q, k, v are pointers to column 0 of their first row plus a ROW STRIDE in floats (>= E), so one pair of
+ *   kernels serves a packed [q | k | v] projection (q = p, k = p + E, v = p + 2E, strides 3E, as wfae_mha_fwd takes it) and
+ *   a separate q with a packed [k | v] (k = kv, v = kv + E, strides 2E, as wfae_sq_attn_fwd takes it).  out (N * Sq, E)
+ *   contiguous.  P = softmax(q . k / sqrt(D)) with the row maximum subtracted; probs (N, H, Sq, Skv) holds P BEFORE
+ *   dropout; dropout on P from the counter-based generator of wfae_dropout / wfae_mha_fwd with mask index
+ *   ((n H + h) Sq + i) Skv + j (for Sq = Skv: wfae_mha_fwd's batch-first indexing).  bwd writes dq, dk, dv through the
+ *   strides of q, k, v (the gradient of a packed projection lands in one buffer); dout (N * Sq, E) contiguous.  No
+ *   atomics, fixed summation order: bitwise repeatable.  With Skv = 1: P == 1, dq == dk == 0 exactly.
+ * gn_act: GroupNorm(G, C) + optional exact GELU in training form.  x (N, C, HW); bias (C) may be NULL and is added to x
+ *   before the statistics (the bias of the convolution in front at no launch); y = act((x + bias - mean) rstd gamma +
+ *   beta), act 0 = none, 1 = GELU (erf form); mean, rstd (N, G) saved; statistics two-pass in fp64 on the group held on
+ *   chip, biased variance, rstd = 1 / sqrt(var + eps).  One launch.  bwd: dx, dgamma, dbeta and — exactly when bias was
+ *   given — dbias = sum over (n, hw) of dx, from dy, x, bias and the two statistics (the activation is recomputed);
+ *   accumulate: add to dgamma / dbeta / dbias.  Per-channel sums over N are finished from ws (wfae_gn_act_bwd_workspace_bytes)
+ *   in a fixed order.  Errors before any launch: C % G != 0 WFAE_ERR_BAD_SHAPE; a group of more than WFAE_GN_MAX_GROUP
+ *   elements (C / G * HW; 16 x 576 = 9216 is inside) WFAE_ERR_UNSUPPORTED; a short workspace WFAE_ERR_WORKSPACE.
+ *   LDS per workgroup: 4 bytes per group element forward, 8 backward (128 KiB at the limit); WFAE_ERR_LAUNCH if the device
+ *   does not grant it.
+ * channel_bias: y[n][c][p] = x[n][c][p] + b[c] (the gradient of b is wfae_reduce_sum).
+ * head_dropout_bcast: attention over ONE key in training: out[n][i][h D + d] = v[n][h D + d] keep(n, h, i) / (1 - p), mask
+ *   index (n H + h) Sq + i — wfae_attn_fwd's at Skv = 1; bwd: dv[n][e] = sum_i dout[n][i][e] keep / (1 - p), i in order. */
+#define WFAE_ATTN_MAX_S 256
+#define WFAE_GN_MAX_GROUP 16384
+int wfae_attn_fwd(const float* q, const float* k, const float* v, float* out, float* probs, int N, int Sq, int Skv, int H,
+                  int D, int64_t q_stride, int64_t k_stride, int64_t v_stride, float p_drop, uint64_t seed,
+                  wfae_stream_t stream);
+int wfae_attn_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout, float* dq, float* dk,
+                  float* dv, int N, int Sq, int Skv, int H, int D, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                  float p_drop, uint64_t seed, wfae_stream_t stream);
+size_t wfae_gn_act_bwd_workspace_bytes(int N, int C);
+int wfae_gn_act_fwd(const float* x, const float* bias /* may be NULL */, const float* gamma, const float* beta, float* y,
+                    float* mean, float* rstd, int N, int C, int HW, int G, float eps, int act, wfae_stream_t stream);
+int wfae_gn_act_bwd(const float* dy, const float* x, const float* bias /* may be NULL */, const float* gamma,
+                    const float* beta, const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta,
+                    float* dbias /* NULL iff bias is */, int N, int C, int HW, int G, int act, int accumulate, void* ws,
+                    size_t ws_bytes, wfae_stream_t stream);
+int wfae_channel_bias_fwd(const float* x, const float* b, float* y, int N, int C, int HW, wfae_stream_t stream);
+int wfae_head_dropout_bcast_fwd(const float* v, float* out, int N, int Sq, int H, int D, float p_drop, uint64_t seed,
+                                wfae_stream_t stream);
+int wfae_head_dropout_bcast_bwd(const float* dout, float* dv, int N, int Sq, int H, int D, float p_drop, uint64_t seed,
+                                wfae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

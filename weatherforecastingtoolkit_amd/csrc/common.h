@@ -120,6 +120,16 @@ __device__ __forceinline__ float gelu_grad_f(float u) {
 }
 __device__ __forceinline__ float sigmoid_f(float v) { return 1.0f / (1.0f + expf(-v)); }
 
+// counter-based RNG (splitmix64 finaliser): uniform [0,1) from (seed, index) — the dropout masks of transformer.hip and
+// convattn.hip; tests/transformer_ref.py restates it
+__device__ __forceinline__ float rng01(unsigned long long seed, unsigned long long idx) {
+  unsigned long long z = seed + idx * 0x9E3779B97F4A7C15ull + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (float)(z >> 40) * (1.0f / 16777216.0f);
+}
+
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 // blocks of 256 threads for a grid-stride loop over n elements, per_thread of them to a thread, at most 4096 blocks
 inline int grid_1d(long n, int per_thread = 4) {

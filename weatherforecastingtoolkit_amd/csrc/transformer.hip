@@ -11,15 +11,6 @@ using namespace wfae;
 
 namespace {
 
-// counter-based RNG (splitmix64 finaliser): uniform [0,1) from (seed, index)
-__device__ __forceinline__ float rng01(unsigned long long seed, unsigned long long idx) {
-  unsigned long long z = seed + idx * 0x9E3779B97F4A7C15ull + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (float)(z >> 40) * (1.0f / 16777216.0f);
-}
-
 // ---------------------------------------------------------------- LayerNorm
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
                                                             const float* __restrict__ g, const float* __restrict__ b,

@@ -873,11 +873,12 @@ class AddFn(Function):
 
 # ------------------------------------------------------- latent transformer --
 class AddLayerNormFn(Function):
-    """LayerNorm(x + res): the post-norm residual of nn.TransformerEncoderLayer."""
+    """LayerNorm(x + res): the post-norm residual of nn.TransformerEncoderLayer.  res None: LayerNorm(x), the norm of a
+    pre-norm layer."""
 
     @staticmethod
     def forward(ctx, x, res, gamma, beta, eps):
-        x, res = _c(x), _c(res)
+        x, res = _c(x), None if res is None else _c(res)
         y, mean, rstd = ops.layernorm_fwd(x, res, gamma, beta, eps)
         ctx.save_for_backward(x, res, gamma, mean, rstd)
         ctx.beta = beta
@@ -888,7 +889,7 @@ class AddLayerNormFn(Function):
         x, res, gamma, mean, rstd = ctx.saved_tensors
         dg, db = grad_buffer(gamma), grad_buffer(ctx.beta)
         dh = ops.layernorm_bwd(_c(dy), x, res, gamma, mean, rstd, dg, db)
-        return dh, dh, dg, db, None
+        return dh, None if res is None else dh, dg, db, None
 
 
 class MhaSeqFirstFn(Function):
@@ -1454,3 +1455,170 @@ class LpipsFn(Function):
                 d = ops.lpips_conv3_bwd_data(d, st.bwd[li], st.cin[li], saved[li - 1][:n] if j else None, st.mode)
                 li -= 1
         return ops.lpips_prep_bwd(d, st.scale, ctx.cx), None, None, None
+
+
+# ---- conv + attention latent autoencoder (csrc/convattn.hip; experiments/v1_experiments/_convattn.py) --------------------
+class AttnFn(Function):
+    """multi-head attention (heads of 16) with separate query / key lengths up to 256 and dropout on the probabilities.
+    kv None: `q` is the packed (n*sq, 3E) projection [q | k | v] of a self-attention (sq == skv); otherwise q is (n*sq, E)
+    and kv the packed (n*skv, 2E) projection [k | v].  Saved: the projections and the probabilities before dropout; the
+    mask is regenerated from `seed`.  The gradient of a packed projection is one buffer."""
+
+    @staticmethod
+    def forward(ctx, q, kv, n, sq, skv, h, p_drop, seed):
+        q = _c(q)
+        kv = None if kv is None else _c(kv)
+        e = q.shape[1] // 3 if kv is None else q.shape[1]
+        d = e // h
+        qv, kk, vv = AttnFn._views(q, kv, e)
+        out, probs = ops.attn_fwd(qv, kk, vv, n, sq, skv, h, d, p_drop, seed)
+        ctx.save_for_backward(q, kv, probs)
+        ctx.cfg = (n, sq, skv, h, d, p_drop, seed)
+        ctx.e = e
+        return out
+
+    @staticmethod
+    def _views(q, kv, e):
+        if kv is None:
+            return q[:, :e], q[:, e:2 * e], q[:, 2 * e:]
+        return q, kv[:, :e], kv[:, e:]
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, kv, probs = ctx.saved_tensors
+        dq = torch.empty_like(q)
+        dkv = None if kv is None else torch.empty_like(kv)
+        ops.attn_bwd(*AttnFn._views(q, kv, ctx.e), probs, _c(dout), *AttnFn._views(dq, dkv, ctx.e), *ctx.cfg)
+        return dq, dkv, None, None, None, None, None, None
+
+
+class GroupNormActFn(Function):
+    """GroupNorm(groups, C) (+ exact GELU with act) of x + bias[c] in training form: one launch forward, the backward
+    entry point gives dx, dgamma, dbeta and the bias gradient.  Saved: x and the (N, G) statistics; the activation is
+    recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, bias, groups, eps, act):
+        x = _c(x)
+        y, mean, rstd = ops.gn_act_fwd(x, gamma, beta, groups, eps, act, bias)
+        ctx.save_for_backward(x, gamma, beta, mean, rstd)
+        ctx.bias, ctx.cfg = bias, (groups, act)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, beta, mean, rstd = ctx.saved_tensors
+        groups, act = ctx.cfg
+        dg, db = grad_buffer(gamma), grad_buffer(beta)
+        dbias = grad_buffer(ctx.bias) if ctx.bias is not None else None
+        dx = ops.gn_act_bwd(_c(dy), x, gamma, beta, mean, rstd, dg, db, groups, act, ctx.bias, dbias)
+        return dx, dg, db, dbias, None, None, None
+
+
+class ChannelBiasFn(Function):
+    """x (N, C, ...) + b (C): the bias of a convolution whose kernel takes none"""
+
+    @staticmethod
+    def forward(ctx, x, b):
+        ctx.b = b
+        return ops.channel_bias_fwd(_c(x), b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _c(dy)
+        db = grad_buffer(ctx.b)
+        n, c = dy.shape[0], dy.shape[1]
+        ops.reduce_sum(dy, n, c, dy.numel() // (n * c), db)
+        return dy, db
+
+
+class HeadDropoutBcastFn(Function):
+    """attention over ONE key in training: v (N, E) -> (N*sq, E), every query position the value row under the head-wise
+    dropout mask of its (identically 1) probability.  At p = 0 this is RepeatRowsFn."""
+
+    @staticmethod
+    def forward(ctx, v, sq, h, p_drop, seed):
+        v = _c(v)
+        ctx.cfg = (v.shape[0], sq, h, p_drop, seed)
+        return ops.head_dropout_bcast_fwd(v, sq, h, p_drop, seed)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return ops.head_dropout_bcast_bwd(_c(dout), *ctx.cfg), None, None, None, None
+
+
+class LinearRowsFn(Function):
+    """y = x w[r0:r1]^T + b[r0:r1]: the part of a packed projection that is live.  The other rows of w and b take no part
+    in the output, and neither does any parameter in `dead` (a norm in front of a projection that is never formed): their
+    gradients are mathematically zero and are written as exact zeros, so the optimiser applies its weight decay and
+    nothing else to them."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, r0, r1, *dead):
+        x = _c(x)
+        ctx.save_for_backward(x, w)
+        ctx.b, ctx.rows, ctx.dead = b, (r0, r1), dead
+        return ops.linear_fwd(x, w[r0:r1], b[r0:r1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        r0, r1 = ctx.rows
+        dy = _c(dy)
+        dw, db = grad_buffer(w).zero_(), grad_buffer(ctx.b).zero_()
+        ops.linear_bwd_weight(dy, x, dw[r0:r1])
+        ops.reduce_sum(dy, dy.shape[0], r1 - r0, 1, db[r0:r1])
+        dx = ops.linear_bwd_data(dy, w[r0:r1]) if ctx.needs_input_grad[0] else None
+        return (dx, dw, db, None, None) + tuple(grad_buffer(p).zero_() for p in ctx.dead)
+
+
+class InProjFn(Function):
+    """the packed in-projection [q | k | v] = x w^T + b of a self-attention.  LinearFn, but for the key bias b[e:2e]: it
+    adds the same q . b_k to every score of a row, which the softmax cancels, so its gradient is mathematically zero (a sum
+    of rounding errors that AdamW would normalise into steps of +-lr) and is written as exact zeros."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, e):
+        x = _c(x)
+        ctx.save_for_backward(x, w)
+        ctx.b, ctx.e = b, e
+        return ops.linear_fwd(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = _c(dy)
+        dw, db = grad_buffer(w), grad_buffer(ctx.b)
+        ops.linear_bwd_weight(dy, x, dw)
+        ops.reduce_sum(dy, dy.shape[0], w.shape[0], 1, db)
+        db[ctx.e:2 * ctx.e].zero_()
+        dx = ops.linear_bwd_data(dy, w) if ctx.needs_input_grad[0] else None
+        return dx, dw, db, None
+
+
+class SplitInProjFn(Function):
+    """the packed in-projection of an attention whose queries and keys come from different tensors:
+    q = xq w[:e]^T + b[:e], kv = xkv w[e:]^T + b[e:] -> (q, kv); the gradient of w (and of b) is one buffer, the key
+    bias's exact zeros (InProjFn)"""
+
+    @staticmethod
+    def forward(ctx, xq, xkv, w, b, e):
+        xq, xkv = _c(xq), _c(xkv)
+        ctx.save_for_backward(xq, xkv, w)
+        ctx.b, ctx.e = b, e
+        return ops.linear_fwd(xq, w[:e], b[:e]), ops.linear_fwd(xkv, w[e:], b[e:])
+
+    @staticmethod
+    def backward(ctx, dq, dkv):
+        xq, xkv, w = ctx.saved_tensors
+        e = ctx.e
+        dq, dkv = _c(dq), _c(dkv)
+        dw, db = grad_buffer(w), grad_buffer(ctx.b)
+        ops.linear_bwd_weight(dq, xq, dw[:e])
+        ops.linear_bwd_weight(dkv, xkv, dw[e:])
+        ops.reduce_sum(dq, dq.shape[0], e, 1, db[:e])
+        ops.reduce_sum(dkv, dkv.shape[0], dkv.shape[1], 1, db[e:])
+        db[e:2 * e].zero_()
+        dxq = ops.linear_bwd_data(dq, w[:e]) if ctx.needs_input_grad[0] else None
+        dxkv = ops.linear_bwd_data(dkv, w[e:]) if ctx.needs_input_grad[1] else None
+        return dxq, dxkv, dw, db, None

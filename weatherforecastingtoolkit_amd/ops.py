@@ -2299,3 +2299,120 @@ def vil_pool_u8_to_f32(src_nhwt, factors, mode="max", xf=None, scale=1.0 / 255.0
           None if xf is None else xf.data_ptr(), _p(dst), n, h, w, t, ft, fh, fw, _POOL_MODES[mode], scale, offset,
           _stream())
     return dst
+
+
+# ---- conv + attention latent autoencoder (include/wfae.h "conv + attention latent autoencoder"; csrc/convattn.hip)
+ATTN_MAX_S, ATTN_D, GN_MAX_GROUP = 256, 16, 16384
+
+
+def _attn_views(what, q, k, v, n, sq, skv, h, d):
+    """row-sliced column views of one projection buffer: 2-D, fp32, unit column stride, (n * s) rows of h * d columns"""
+    e = h * d
+    for name, t, s in (("q", q, sq), ("k", k, skv), ("v", v, skv)):
+        if not t.is_cuda:
+            raise _lib.WfaeError("wfae kernels need device tensors (the HIP path has no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise _lib.WfaeError(f"wfae kernels are fp32, got {t.dtype}")
+        if t.dim() != 2 or tuple(t.shape) != (n * s, e) or t.stride(1) != 1 or t.stride(0) < e:
+            raise _lib.WfaeError(f"{what}: {name} of shape {tuple(t.shape)} / strides {tuple(t.stride())}, expected "
+                                 f"({n * s}, {e}) rows with unit column stride")
+
+
+def attn_fwd(q, k, v, n, sq, skv, h, d, p_drop=0.0, seed=0):
+    """q (n*sq, h*d), k, v (n*skv, h*d): contiguous tensors or column slices of a packed projection (row stride = the packed
+    width) -> (out (n*sq, h*d), probs (n, h, sq, skv) before dropout)"""
+    _attn_views("attn_fwd", q, k, v, n, sq, skv, h, d)
+    out = torch.empty((n * sq, h * d), dtype=torch.float32, device=q.device)
+    probs = torch.empty((n, h, sq, skv), dtype=torch.float32, device=q.device)
+    _call("wfae_attn_fwd", 4 * n * h * sq * skv * d, 4 * (q.numel() + k.numel() + v.numel() + out.numel() + 2 * probs.numel()),
+          _p(q), _p(k), _p(v), _p(out), _p(probs), n, sq, skv, h, d, q.stride(0), k.stride(0), v.stride(0), p_drop, seed,
+          _stream())
+    return out, probs
+
+
+def attn_bwd(q, k, v, probs, dout, dq, dk, dv, n, sq, skv, h, d, p_drop=0.0, seed=0):
+    """dq, dk, dv: views with the row strides of q, k, v (the gradient of a packed projection lands in one buffer)"""
+    _attn_views("attn_bwd", q, k, v, n, sq, skv, h, d)
+    _attn_views("attn_bwd", dq, dk, dv, n, sq, skv, h, d)
+    if (dq.stride(0), dk.stride(0), dv.stride(0)) != (q.stride(0), k.stride(0), v.stride(0)):
+        raise _lib.WfaeError("attn_bwd: dq, dk, dv must have the row strides of q, k, v")
+    _chk(probs, dout)
+    if tuple(probs.shape) != (n, h, sq, skv) or tuple(dout.shape) != (n * sq, h * d):
+        raise _lib.WfaeError(f"attn_bwd: probs {tuple(probs.shape)} / dout {tuple(dout.shape)}, expected "
+                             f"({n}, {h}, {sq}, {skv}) and ({n * sq}, {h * d})")
+    _call("wfae_attn_bwd", 10 * n * h * sq * skv * d, 4 * (2 * (q.numel() + k.numel() + v.numel()) + dout.numel() + 3 * probs.numel()),
+          _p(q), _p(k), _p(v), _p(probs), _p(dout), _p(dq), _p(dk), _p(dv), n, sq, skv, h, d, q.stride(0), k.stride(0),
+          v.stride(0), p_drop, seed, _stream())
+
+
+def _gn_dims(what, x, gamma, beta, bias, d=""):
+    """(N, C, HW) of x; the per-channel vectors (with d = "d": their gradients) are checked against C"""
+    if x.dim() < 3:
+        raise _lib.WfaeError(f"{what}: expected (N, C, ...), got {tuple(x.shape)}")
+    n, c = x.shape[0], x.shape[1]
+    hw = x.numel() // max(n * c, 1)
+    for name, t in (("gamma", gamma), ("beta", beta), ("bias", bias)):
+        if t is not None and tuple(t.shape) != (c,):
+            raise _lib.WfaeError(f"{what}: {d}{name} of shape {tuple(t.shape)} against {c} channels")
+    return n, c, hw
+
+
+def gn_act_fwd(x, gamma, beta, groups, eps=1e-5, act=0, bias=None):
+    """-> (y, mean (N, G), rstd (N, G)): y = act(GroupNorm(x + bias[c])), act 0 none / 1 exact GELU"""
+    _chk(x, gamma, beta, bias)
+    n, c, hw = _gn_dims("gn_act_fwd", x, gamma, beta, bias)
+    y = torch.empty_like(x)
+    mean = torch.empty((n, groups), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((n, groups), dtype=torch.float32, device=x.device)
+    _call("wfae_gn_act_fwd", 0, 8 * x.numel(), _p(x), _p(bias), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), n, c, hw,
+          int(groups), float(eps), int(act), _stream())
+    return y, mean, rstd
+
+
+def gn_act_bwd(dy, x, gamma, beta, mean, rstd, dgamma, dbeta, groups, act=0, bias=None, dbias=None, accumulate=False):
+    """-> dx; dgamma, dbeta (and dbias when a bias was given) are written, or added to with accumulate"""
+    _chk(dy, x, gamma, beta, mean, rstd, dgamma, dbeta, bias, dbias)
+    n, c, hw = _gn_dims("gn_act_bwd", x, gamma, beta, bias)
+    _gn_dims("gn_act_bwd", x, dgamma, dbeta, dbias, "d")
+    if dy.shape != x.shape or tuple(mean.shape) != (n, groups) or tuple(rstd.shape) != (n, groups):
+        raise _lib.WfaeError(f"gn_act_bwd: dy {tuple(dy.shape)} / statistics {tuple(mean.shape)} against x {tuple(x.shape)}")
+    dx = torch.empty_like(x)
+    ws = workspace(_lib.load().wfae_gn_act_bwd_workspace_bytes(n, c))
+    _call("wfae_gn_act_bwd", 0, 12 * x.numel(), _p(dy), _p(x), _p(bias), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx),
+          _p(dgamma), _p(dbeta), _p(dbias), n, c, hw, int(groups), int(act), int(accumulate), ws.data_ptr(), ws.numel(),
+          _stream())
+    return dx
+
+
+def channel_bias_fwd(x, b):
+    """x (N, C, ...) + b (C)"""
+    _chk(x, b)
+    if x.dim() < 2 or tuple(b.shape) != (x.shape[1],):
+        raise _lib.WfaeError(f"channel_bias_fwd: x {tuple(x.shape)} against a bias of shape {tuple(b.shape)}")
+    n, c = x.shape[0], x.shape[1]
+    y = torch.empty_like(x)
+    _call("wfae_channel_bias_fwd", 0, 8 * x.numel(), _p(x), _p(b), _p(y), n, c, x.numel() // (n * c), _stream())
+    return y
+
+
+def head_dropout_bcast_fwd(v, sq, h, p_drop=0.0, seed=0):
+    """v (N, E) -> (N * sq, E): attention over one key, the value row under the head-wise dropout mask of its probabilities"""
+    _chk(v)
+    if v.dim() != 2 or v.shape[1] % h != 0:
+        raise _lib.WfaeError(f"head_dropout_bcast_fwd: v {tuple(v.shape)} against {h} heads")
+    n, e = v.shape
+    out = torch.empty((n * sq, e), dtype=torch.float32, device=v.device)
+    _call("wfae_head_dropout_bcast_fwd", 0, 4 * (v.numel() + out.numel()), _p(v), _p(out), n, sq, h, e // h, p_drop, seed,
+          _stream())
+    return out
+
+
+def head_dropout_bcast_bwd(dout, n, sq, h, p_drop=0.0, seed=0):
+    _chk(dout)
+    if dout.dim() != 2 or dout.shape[0] != n * sq or dout.shape[1] % h != 0:
+        raise _lib.WfaeError(f"head_dropout_bcast_bwd: dout {tuple(dout.shape)} against N = {n}, Sq = {sq}, {h} heads")
+    e = dout.shape[1]
+    dv = torch.empty((n, e), dtype=torch.float32, device=dout.device)
+    _call("wfae_head_dropout_bcast_bwd", 0, 4 * (dv.numel() + dout.numel()), _p(dout), _p(dv), n, sq, h, e // h, p_drop, seed,
+          _stream())
+    return dv
