@@ -296,12 +296,12 @@ def g3b_f32_supported(c, wgrad):
 
 
 def r_g3b_fwd_f32(c):
-    """ops.py:1140 -> g3b.hip:656 g3b_launch<16, 6, 96, 3, 3, float>"""
+    """ops.gconv3x3_fwd (fp32 branch) -> g3b.hip:656 g3b_launch<16, 6, 96, 3, 3, float>"""
     return c.ep in ("g3_fwd", "g3_dgrad") and c.storage == "f32" and c.g3b and g3b_f32_supported(c, False)
 
 
 def r_g3b_fwd_bf16(c):
-    """ops.py:1144 (ops.g3b_supported: the switch, 'medium', g3b.hip:591) -> g3b.hip:598"""
+    """ops.gconv3x3_fwd (bf16 branch; ops.g3b_supported: the switch, 'medium', g3b.hip:591) -> g3b.hip:598"""
     return c.ep in ("g3_fwd", "g3_dgrad") and c.storage == "bf16" and c.g3b and c.precision == "medium" and g3b_supported(c)
 
 
@@ -378,17 +378,17 @@ def _wgrad_valu_taken(c):
 
 
 def r_g3b_wgrad_f32(c):
-    """ops.py:1158 -> g3b.hip:671"""
+    """ops.gconv3x3_bwd_weight (fp32 branch) -> g3b.hip:671"""
     return c.ep == "g3_wgrad" and c.storage == "f32" and c.g3b and g3b_f32_supported(c, True)
 
 
 def r_g3b_wgrad_bf16(c):
-    """ops.py:1162 -> g3b.hip:619"""
+    """ops.gconv3x3_bwd_weight (bf16 branch, g3b) -> g3b.hip:619"""
     return c.ep == "g3_wgrad" and c.storage == "bf16" and c.g3b and c.precision == "medium" and g3b_supported(c)
 
 
 def r_gconv3_wgrad_bf16(c):
-    """ops.py:1166 -> gemm.hip:1796: the MFMA kernel on bf16 tensors, no fallback"""
+    """ops.gconv3x3_bwd_weight (bf16 branch, g3b not taken) -> gemm.hip:1796: the MFMA kernel on bf16 tensors, no fallback"""
     return c.ep == "g3_wgrad" and c.storage == "bf16" and not r_g3b_wgrad_bf16(c) and _wgrad_mfma_taken(c)
 
 
@@ -528,7 +528,7 @@ def r_dconv_wgrad(ks, stride, ob):
 
 def r_dconv_bf16(ep, first=False):
     def pred(c):
-        """ops.py:1021-1036, :1048, :1065-1076 -> dconv.hip:496-531: the first layer (fp32 frame -> bf16), the output
+        """ops.dconv_fwd, ops.dconv_bwd_data, ops.dconv_bwd_weight -> dconv.hip:496-531: the first layer (fp32 frame -> bf16), the output
         convolution (bf16 -> fp32), its data gradient (-> bf16) and their weight gradients (the big tensor bf16)"""
         if c.ep != ep or c.storage != "bf16":
             return False
@@ -549,7 +549,7 @@ def r_dconv_bf16(ep, first=False):
 
 def r_simple(ep):
     def pred(c):
-        """gemm.hip:1730 / :1748 / :1771 (Winograd off: ops.py:969-1006 fall through to the gather GEMMs) and gemm.hip:1868 /
+        """gemm.hip:1730 / :1748 / :1771 (Winograd off: ops.conv4x4s2_down / _up / _wgrad fall through to the gather GEMMs) and gemm.hip:1868 /
         :1907 (the flat-shift 4x4 stride-1 GEMMs: the channels read must be a multiple of 16, gemm.hip:1875)"""
         if c.ep != ep or c.storage != "f32":
             return False

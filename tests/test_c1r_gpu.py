@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from tests._util import relerr
+from tests.c1_golden import rec
 
 pytestmark = pytest.mark.gpu
 
@@ -52,6 +53,9 @@ def test_c1r_forward_and_data_gradient_match_fp64_like_the_fp32_kernels(ops, dev
     if (m, k) in FWD_SHAPES:
         assert torch.equal(res[True][0], ops.conv1x1_fwd(x, wt))
     assert not torch.equal(res[True][0], res[False][0]), "c1r did not run (same bits as gemm.hip)"
+    with rec.Recorder() as launches:      # ... and the trace says it directly
+        ops.conv1x1_fwd(x, wt), ops.conv1x1_bwd_data(x, wt_t)
+    assert [ln.split()[0] for ln in launches] == ["wfae_c1r_fwd", "wfae_c1r_fwd"]
     for i, ref in enumerate((ref_f, ref_d)):
         e_old, e_new = err64(res[False][i], ref), err64(res[True][i], ref)
         assert e_new <= max(2.0 * e_old, 2e-6), (i, e_new, e_old)

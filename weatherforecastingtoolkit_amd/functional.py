@@ -556,37 +556,40 @@ def _mk_stats(mean, invstd, scale, shift):
     return st
 
 
-def _b16(w, plane, transposed, x, st=None, res=None, stats=False, label="wfae_c1b_fwd"):
-    """a Bottleneck 1x1 product on bf16-stored tensors: csrc/c1rb.hip (register-direct, reads the fp32 weight) where it
-    serves the shape, else csrc/c1b.hip with the prepared bf16 plane"""
-    m = w.shape[1] if transposed else w.shape[0]
-    if ops.c1rb_take(m, x.shape[1], x.shape[2] * x.shape[3], st is not None):
-        return ops.c1rb_fwd(w, transposed, x, st, res, stats, label)
-    return ops.c1b_fwd(plane, x, st, res, stats, label)
+def _storage(t):
+    return "bf16" if t.dtype == ops.BF16 else "f32"
+
+
+def _c1(w, plane, transposed, x, st=None, res=None, stats=False, fam=None):
+    """a Bottleneck 1x1 product y = A f(x) (+ res), A = w or, transposed, w^T (the data gradient), on the kernel family
+    ops.conv1x1_route names for it (`fam`: the caller has asked already) -> (y, StatRows | None).  `plane`: the bf16 plane of
+    ops.c1b_weights that is A, which csrc/c1b.hip takes (a caller without one gets gemm.hip)"""
+    if fam is None:
+        fam = ops.conv1x1_route("dgrad" if transposed else "fwd", w.shape[1] if transposed else w.shape[0], x.shape[1],
+                                x.shape[2] * x.shape[3], _storage(x), st is not None, False, "none" if res is None else "ordinary")
+    if fam == "c1b" and (plane is None or plane.numel() == 0):
+        fam = "gemm"
+    label = None if fam in ("c1r", "gemm") else "wfae_c1b_dgrad" if transposed else "wfae_c1b_fwd"
+    return ops._c1_launch(fam, plane if fam == "c1b" else w, transposed, x, st, None, res, False, stats, label)
+
+
+_b16 = _c1      # (the name tests/ reach it by: it served the bf16-stored tensors only)
 
 
 def _dgrad_bn(dt, w, Wt, x, gamma, st, dgamma, dbeta, res, training):
     """dx of  conv1x1(gelu(bn(x)), w)  given dt = dL/d(conv output): the data gradient dA = W^T dT followed by the
-    BatchNorm + GELU backward at x (+ res, the residual-branch gradient).  bf16-stored tensors: csrc/c1rb.hip, or csrc/c1b.hip
-    with Wt, the bf16 plane of w^T; fp32 storage (Wt empty): wfae_conv1x1_bwd_data."""
-    if dt.dtype == torch.float32 and ops.c1r_bnred_supported(w.shape[1], dt.shape[1], dt.shape[2] * dt.shape[3]):
+    BatchNorm + GELU backward at x (+ res, the residual-branch gradient); Wt: the bf16 plane of w^T for csrc/c1b.hip, or empty"""
+    how = ops.conv1x1_dgrad_bn_route(w.shape[1], dt.shape[1], dt.shape[2] * dt.shape[3], _storage(dt))
+    if how is not None:
         # the C <= 256 widening data gradients on csrc/c1r.hip: sum dU / sum dU xhat of the BatchNorm in front ride in the epilogue
-        # (x travels through the kernel's residual ring), the reduce pass over (dA, x) disappears
-        # — and so does dA itself: the second pass runs in the epilogue of the same product computed again (ops.c1r_bndx)
-        if ops.c1r_bndx_on():
-            _, sr = ops.c1r_bnred(w, dt, x, st, store=False)
-            ops.bn_act_bwd_from_rows(sr, x.shape[1], dgamma, dbeta)
-            return ops.c1r_bndx(w, dt, x, gamma, st, res, training)
-        da, sr = ops.c1r_bnred(w, dt, x, st)
+        # (x travels through the kernel's residual ring), the reduce pass over (dA, x) disappears — and with 'bndx' so does dA
+        # itself: the second pass runs in the epilogue of the same product computed again
+        da, sr = ops.c1r_bnred(w, dt, x, st, store=how == "bnred")
         ops.bn_act_bwd_from_rows(sr, x.shape[1], dgamma, dbeta)
+        if how == "bndx":
+            return ops.c1r_bndx(w, dt, x, gamma, st, res, training)
         return ops.bn_act_bwd_dx(da, x, gamma, st, res, 1, training)
-    if dt.dtype == ops.BF16 and ops.c1rb_supported(w.shape[1], dt.shape[1], dt.shape[2] * dt.shape[3]):
-        da = ops.c1rb_fwd(w, True, dt, label="wfae_c1b_dgrad")
-    elif Wt is not None and Wt.numel() > 0 and Wt.dtype == ops.BF16:
-        da = ops.c1b_fwd(Wt, dt, label="wfae_c1b_dgrad")
-    else:
-        da = ops.conv1x1_bwd_data(dt, w)
-    return ops.bn_act_bwd(da, x, gamma, st, dgamma, dbeta, res, 1, training)
+    return ops.bn_act_bwd(_c1(w, Wt, True, dt)[0], x, gamma, st, dgamma, dbeta, res, 1, training)
 
 
 class BottleneckFn(Function):
@@ -608,52 +611,37 @@ class BottleneckFn(Function):
         fuse = training and STAT_FUSION
         emit = fuse and getattr(mod, "emit_stats", False)
         C, mid, hw = x.shape[1], w1.shape[0], x.shape[2] * x.shape[3]
-        # bf16 storage: csrc/c1b.hip serves the four 1x1 products — (M = mid, K = C): the C -> C/4 forward and the C/4 -> C data
-        # gradient; (M = C, K = mid): the C/4 -> C forward and the C -> C/4 data gradient — with one bf16 weight plane each way,
-        # written once here and reused in backward
-        W1p = W3p = (None, None)
-        bf = x.dtype == ops.BF16
-        rb1, rb3 = bf and ops.c1rb_supported(mid, C, hw), bf and ops.c1rb_supported(C, mid, hw)   # register-direct (csrc/c1rb.hip)
-        cb1 = rb1 or (bf and ops.c1b_supported(mid, C, hw))
-        cb3 = rb3 or (bf and ops.c1b_supported(C, mid, hw))
-        if C >= 256:
-            rb1 = False        # the C -> C/4 forward with the prologue runs on c1b there (ops.c1rb_take), so its plane pair is needed
-        if (cb1 and not rb1) or (cb3 and not rb3):      # c1b.hip takes prepared bf16 planes; c1rb.hip reads the fp32 weight itself
-            W1p, W3p = ops.c1b_weights(w1), ops.c1b_weights(w3)
+        sto = _storage(x)
+
+        def route(op, m, k, pro=False, res="none"):
+            return ops.conv1x1_route(op, m, k, hw, sto, pro, False, res)
+        # the routes of the 1x1 products, each asked once (host time per block shows in the step) — (M = mid, K = C): the
+        # C -> C/4 forward r1 and the C/4 -> C data gradient d3; (M = C, K = mid): the C/4 -> C forward r3 and the C -> C/4 data
+        # gradient d1
+        fused1 = FUSE_A1 and C <= FUSE_A1_MAXC and ops.conv1x1_bnact_supported(x, mid)
+        r1, r3 = route("fwd", mid, C, fused1), route("fwd", C, mid, True, "ordinary")
+        fused3 = (FUSE_A3 and C <= (FUSE_A3_MAXC_C1R if r3 in ("c1r", "c1rb") else FUSE_A3_MAXC)     # register-direct: see above
+                  and ops.conv1x1_bnact_supported((x.shape[0], mid) + x.shape[2:], C))
+        if not fused3:
+            r3 = route("fwd", C, mid, False, "ordinary")
+        # csrc/c1b.hip takes a bf16 weight plane each way (they exist for bf16-stored tensors only): both pairs are written once
+        # here when a product of the block routes to it, and a transposed plane is kept for the data gradient that does
+        d1, d3 = (route("dgrad", C, mid), route("dgrad", mid, C)) if sto == "bf16" else (None, None)
+        W1p, W3p = (ops.c1b_weights(w1), ops.c1b_weights(w3)) if "c1b" in (r1, r3, d1, d3) else ((None, None), (None, None))
         st1 = _bn_stats_rows(x_stats if (fuse or isinstance(x_stats, ops.StatParts)) else None, x, bn1, training)
-        fused1 = FUSE_A1 and x.shape[1] <= FUSE_A1_MAXC and ops.conv1x1_bnact_supported(x, w1.shape[0])
         a1 = None if fused1 else ops.bn_act_fwd(x, st1, 1)
-        if cb1:
-            src, pro = (x, st1) if fused1 else (a1, None)
-            t1, sr2 = _b16(w1, W1p[0], False, src, pro, None, True) if fuse else (_b16(w1, W1p[0], False, src, pro), None)
-        elif fused1:
-            t1, sr2 = ops.conv1x1_fwd_bnact(x, st1, w1, stats=True) if fuse else (ops.conv1x1_fwd_bnact(x, st1, w1), None)
-        else:
-            t1, sr2 = ops.conv1x1_fwd_stats(a1, w1) if fuse else (ops.conv1x1_fwd(a1, w1), None)
+        t1, sr2 = _c1(w1, W1p[0], False, *((x, st1) if fused1 else (a1, None)), None, fuse, r1)
         st2 = _bn_stats_rows(sr2, t1, bn2, training)
         a2 = ops.bn_act_fwd(t1, st2, 1)
         t2 = _g3_fwd(a2, wg, groups)
         st3 = _bn_stats(t2, bn3, training)
-        reg_direct = ops.c1r_supported(C, mid, hw) if x.dtype == torch.float32 else (bf and ops.c1rb_supported(C, mid, hw))
-        a3_maxc = FUSE_A3_MAXC_C1R if reg_direct else FUSE_A3_MAXC
-        if FUSE_A3 and w3.shape[0] <= a3_maxc and ops.conv1x1_bnact_supported(t2, w3.shape[0]):
-            a3 = None
-            if cb3:
-                y, mod._out_stats = _b16(w3, W3p[0], False, t2, st3, x, True) if emit else (_b16(w3, W3p[0], False, t2, st3, x), None)
-            else:
-                y, mod._out_stats = ops.conv1x1_fwd_bnact(t2, st3, w3, None, x, stats=True) if emit else \
-                    (ops.conv1x1_fwd_bnact(t2, st3, w3, None, x), None)
-        else:
-            a3 = ops.bn_act_fwd(t2, st3, 1)
-            if cb3:
-                y, mod._out_stats = _b16(w3, W3p[0], False, a3, None, x, True) if emit else (_b16(w3, W3p[0], False, a3, None, x), None)
-            else:
-                y, mod._out_stats = ops.conv1x1_fwd_stats(a3, w3, None, x) if emit else (ops.conv1x1_fwd(a3, w3, None, x), None)
+        a3 = None if fused3 else ops.bn_act_fwd(t2, st3, 1)
+        y, mod._out_stats = _c1(w3, W3p[0], False, *((t2, st3) if fused3 else (a3, None)), x, emit, r3)
         ctx.save_for_backward(x, _opt(a1), t1, a2, t2, _opt(a3), g1, w1, g2, wg, g3, w3,
                               st1.mean, st1.invstd, st1.scale, st1.shift,
                               st2.mean, st2.invstd, st2.scale, st2.shift,
                               st3.mean, st3.invstd, st3.scale, st3.shift,
-                              _opt(W1p[1] if (cb3 and not rb3) else None), _opt(W3p[1] if (cb1 and not rb1) else None))
+                              _opt(W1p[1] if d1 == "c1b" else None), _opt(W3p[1] if d3 == "c1b" else None))
         ctx.training = training
         ctx.groups = groups
         ctx.betas = (b1, b2, b3)

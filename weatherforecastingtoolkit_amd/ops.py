@@ -6,6 +6,7 @@ through ctypes.  All tensors must be CUDA(HIP) fp32 and contiguous (NCHW).
 """
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
@@ -83,36 +84,37 @@ def _planes_peak(planes):
     return PEAK_BF16_MFMA / 6 if planes == 3 else PEAK_BF16_MFMA
 
 
-# matrix-instruction ceiling per GEMM-family entry point, from its C argument list (positions as in include/wfae.h)
-_PEAK_OF = {
-    "wfae_conv1x1_fwd": lambda a: _gemm_peak(a[8], a[7]),                 # (.., NB, Cin, Cout, HW): M = Cout, K = Cin
-    "wfae_conv1x1_fwd_stats": lambda a: _gemm_peak(a[8], a[7]),
-    "wfae_conv1x1_fwd_bnact": lambda a: _gemm_peak(a[10], a[9]),
-    "wfae_conv1x1_fwd_bf16": lambda a: PEAK_BF16_MFMA,
-    "wfae_conv1x1_bwd_data": lambda a: _gemm_peak(a[4], a[5]),            # M = Cin, K = Cout
-    "wfae_conv1x1_bwd_data_bf16": lambda a: PEAK_BF16_MFMA,
+def _peak_table():
+    """matrix-instruction ceiling per GEMM-family entry point from its C arguments, found by the NAMES include/wfae.h gives
+    them: a name the header does not have raises here, at import, not at the first profiled launch"""
+    decls = _lib.parse_header()
+
+    def at(entry, name):
+        if name not in decls[entry][2]:
+            raise _lib.WfaeError(f"include/wfae.h: {entry} has no argument named {name}")
+        return decls[entry][2].index(name)
+
+    t = {}
+    for mk, entries in ((("Cout", "Cin"), "conv1x1_fwd conv1x1_fwd_stats conv1x1_fwd_bnact"), (("Cin", "Cout"), "conv1x1_bwd_data"),
+                        (("Out", "In"), "linear_fwd"), (("In", "Out"), "linear_bwd_data linear_bwd_data_splitk"),
+                        (("Out", "B"), "linear_bwd_weight linear_bwd_weight_splitk")):
+        for e in entries.split():
+            t["wfae_" + e] = lambda a, i=at("wfae_" + e, mk[0]), j=at("wfae_" + e, mk[1]): _gemm_peak(a[i], a[j])
     # weight gradients: M = Cout, or Cin when the roles are swapped (Cin < Cout and Cin < 128); K = the pixels
-    "wfae_conv1x1_bwd_weight": lambda a: _gemm_peak(a[4] if (a[4] < a[5] and a[4] < 128) else a[5], 1 << 20),
-    "wfae_conv1x1_bwd_weight_bnact": lambda a: _gemm_peak(a[6] if (a[6] < a[7] and a[6] < 128) else a[7], 1 << 20),
-    "wfae_conv1x1_bwd_weight_bf16": lambda a: PEAK_BF16_MFMA,
-    "wfae_linear_fwd": lambda a: _gemm_peak(a[6], a[5]),
-    "wfae_linear_bwd_data": lambda a: _gemm_peak(a[4], a[5]),
-    "wfae_linear_bwd_data_splitk": lambda a: _gemm_peak(a[4], a[5]),
-    "wfae_linear_bwd_weight": lambda a: _gemm_peak(a[5], a[3]),
-    "wfae_linear_bwd_weight_splitk": lambda a: _gemm_peak(a[5], a[3]),
-    "wfae_wino_gemm_down_split": lambda a: _planes_peak(a[4]),
-    "wfae_wino_gemm_up_split": lambda a: _planes_peak(a[4]),
-    "wfae_wino_gemm_wgrad_split": lambda a: _planes_peak(a[4]),
-    "wfae_wino_gemm_down": lambda a: _default_peak(),
-    "wfae_wino_gemm_up": lambda a: _default_peak(),
-    "wfae_wino_gemm_wgrad": lambda a: _default_peak(),
-    "wfae_split_gemm": lambda a: _planes_peak(a[1]),
-    "wfae_conv4x4s2_down": lambda a: _default_peak(),
-    "wfae_conv4x4s2_up": lambda a: _default_peak(),
-    "wfae_conv4x4s2_wgrad": lambda a: _default_peak(),
-    "wfae_conv4x4s1_fwd": lambda a: _gemm_peak(a[5], 16 * a[4]),
-    "wfae_conv4x4s1_bwd_weight": lambda a: _gemm_peak(a[5], 1 << 20),
-}
+    for e in ("wfae_conv1x1_bwd_weight", "wfae_conv1x1_bwd_weight_bnact"):
+        t[e] = lambda a, i=at(e, "Cin"), j=at(e, "Cout"): _gemm_peak(a[i] if (a[i] < a[j] and a[i] < 128) else a[j], 1 << 20)
+    for e in ("wfae_wino_gemm_down_split", "wfae_wino_gemm_up_split", "wfae_wino_gemm_wgrad_split", "wfae_split_gemm"):
+        t[e] = lambda a, i=at(e, "planes"): _planes_peak(a[i])
+    for e in "wino_gemm_down wino_gemm_up wino_gemm_wgrad conv4x4s2_down conv4x4s2_up conv4x4s2_wgrad".split():
+        t["wfae_" + e] = lambda a: _default_peak()
+    for e in ("wfae_conv1x1_fwd_bf16", "wfae_conv1x1_bwd_data_bf16", "wfae_conv1x1_bwd_weight_bf16"):
+        t[e] = lambda a: PEAK_BF16_MFMA
+    t["wfae_conv4x4s1_fwd"] = lambda a, i=at("wfae_conv4x4s1_fwd", "Cout"), j=at("wfae_conv4x4s1_fwd", "Cin"): _gemm_peak(a[i], 16 * a[j])
+    t["wfae_conv4x4s1_bwd_weight"] = lambda a, i=at("wfae_conv4x4s1_bwd_weight", "Cout"): _gemm_peak(a[i], 1 << 20)
+    return t
+
+
+_PEAK_OF = _peak_table()
 
 
 def workspace(min_bytes: int = 0):
@@ -208,10 +210,44 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-# ----------------------------------------------- 1x1 conv, register-direct (c1r)
-# csrc/c1r.hip: the Bottleneck's four 1x1 products on fp32 tensors at the C <= 256 stages (activation HBM -> registers ->
-# bf16 matrix core with exact three-plane operands, no LDS staging).  The wfae_conv1x1_* wrappers below route to it.
-_C1R = True   # A/B through set_c1r()
+class StatRows:
+    """partial BatchNorm sums written by a GEMM epilogue: `part` (float64) = sum[rows][C] ++ sumsq[rows][C]"""
+    __slots__ = ("part", "rows")
+
+    def __init__(self, part, rows):
+        self.part, self.rows = part, rows
+
+
+class StatParts:
+    """fp64 partial BatchNorm sums left by a producer kernel: `part` = [splits][C][2] doubles (sum, sum of squares)"""
+    __slots__ = ("part", "splits")
+
+    def __init__(self, part, splits):
+        self.part, self.splits = part, splits
+
+
+def _rows_out(n, device):
+    """an fp64 partial buffer of n doubles and the int a launcher writes its row / split count to (a HOST pointer) ->
+    (part, count, the three C arguments (part, capacity, &count)); read count.value after the call"""
+    part = torch.empty(n, dtype=torch.float64, device=device)
+    count = ctypes.c_int(0)
+    return part, count, (part.data_ptr(), n, ctypes.cast(ctypes.pointer(count), ctypes.c_void_p))
+
+
+_NO_ROWS = (None, 0, None)
+
+
+# ------------------------------------------------------------- 1x1 products
+# y[n, M, p] = sum_k A[M, k] f(x[n, k, p]) (+ bias) (+ res): the forward convolution (A = w), its data gradient (A = w^T) and
+# its weight gradient, on six kernel families.  conv1x1_route names the family of a product, _c1_launch / _c1_wgrad launch it.
+#   c1r   csrc/c1r.hip   fp32 tensors, register-direct (activation HBM -> registers -> bf16 matrix core with exact three-plane
+#                        operands, no LDS staging): the Bottleneck shapes with HW % 64 == 0, fp32 precision, split GEMMs on
+#   c1rb  csrc/c1rb.hip  the same on bf16-stored tensors ('medium'), HW % 128 == 0; reads the fp32 weight
+#   c1b   csrc/c1b.hip   bf16-stored tensors, LDS-tiled, takes the bf16 weight planes of c1b_weights
+#   c1w   csrc/c1w.hip   weight gradients, both operands as K-contiguous rows (no LDS transpose)
+#   gemm  csrc/gemm.hip  everything else; the library itself hands the narrowing products of the C >= 512 stages on fp32
+#                        tensors to csrc/c1n.hip (set_c1n), see conv1x1_route
+_C1R = _C1R_BNRED = _C1R_BNDX = _C1RB = _C1B = _C1W = True   # A/B switches, through the set_* functions below
 
 
 def set_c1r(on):
@@ -220,74 +256,296 @@ def set_c1r(on):
     _C1R = bool(on)
 
 
-def c1r_supported(m, k, hw):
-    return (_C1R and _SPLIT_GEMM and _lib.load().wfae_get_matmul_precision() == 0
-            and bool(_lib.load().wfae_c1r_supported(int(m), int(k), int(hw))))
-
-
-def _c1r_take(m, k, hw, dgrad):
-    """route this product to c1r?  Every shape it serves (profiles/r04_kbench_c1r_variants.txt, r04_kbench_c1r_knobs.txt): at
-    C = 256 gemm.hip's kernels are bound by the fp32 MFMA instruction and c1r wins all four products (0.346 -> 0.31, 0.445 ->
-    0.30, 0.685 -> 0.49, 0.500 -> 0.40 - 0.45 ms); at C = 128 both are HBM-bound: c1r wins the forward launches, which carry a
-    BatchNorm + GELU prologue and / or a residual + BatchNorm-sum epilogue in the step (0.72 -> 0.65, 1.14 -> 1.02 ms), and
-    ties the two plain data gradients (0.54 - 0.59 vs 0.57 - 0.59 ms) — one kernel family per stage, and every form of a
-    shape on the same kernel keeps fused and unfused forms bit-identical.  The M-sliced shapes of the C >= 512 stages serve the
-    widening products in both directions (profiles/r04_kbench_c1r_sliced.txt)."""
-    return c1r_supported(m, k, hw)
-
-
-def _c1r(w, transposed, x, st, res, stats, label):
-    """y = A f(x) (+ res): A = w (Cout, Cin) or, transposed, w^T (the data gradient); -> y | (y, StatRows)"""
-    import ctypes
-    nb, k, h, wd = x.shape
-    cout, cin = w.shape[0], w.shape[1]
-    m, sm, sk = (cin, 1, cin) if transposed else (cout, cin, 1)
-    y = torch.empty((nb, m, h, wd), dtype=torch.float32, device=x.device)
-    fl = 2 * nb * h * wd * k * m
-    by = 4 * (nb * h * wd * (k + m) + k * m) + (0 if res is None else 4 * nb * h * wd * m)
-    ps, ph = (None, None) if st is None else (_p(st.scale), _p(st.shift))
-    if not stats:
-        _call("wfae_c1r_fwd", fl, by, _p(w), sm, sk, _p(x), ps, ph, _p(res), _p(y), nb, k, m, h * wd, None, 0, None, _stream(),
-              label=label, peak=PEAK_BF16_MFMA / 6)
-        return y
-    rows_n = int(_lib.load().wfae_c1r_stat_rows(m, k, nb, h * wd))
-    part = torch.empty(2 * rows_n * m, dtype=torch.float64, device=x.device)
-    rows = ctypes.c_int(0)
-    _call("wfae_c1r_fwd", fl, by, _p(w), sm, sk, _p(x), ps, ph, _p(res), _p(y), nb, k, m, h * wd, part.data_ptr(), part.numel(),
-          ctypes.cast(ctypes.pointer(rows), ctypes.c_void_p), _stream(), label=label, peak=PEAK_BF16_MFMA / 6)
-    return y, StatRows(part[:2 * rows.value * m], rows.value)     # (the capacity is sized for the widest user of the shape)
-
-
-_C1R_BNRED = True   # A/B through set_c1r_bnred()
-
-
 def set_c1r_bnred(on):
     """A/B switch: the reductions of the first BatchNorm's backward pass in the epilogue of the c1r data gradient (C <= 256)"""
     global _C1R_BNRED
     _C1R_BNRED = bool(on)
 
 
+def set_c1r_bndx(on):
+    """A/B switch: the second pass of the first BatchNorm's backward in the epilogue of a recomputed data gradient (c1r_bndx)
+    or as bn_act_bwd_dx over the stored one"""
+    global _C1R_BNDX
+    _C1R_BNDX = bool(on)
+
+
+def set_c1n(on):
+    """A/B switch: the fp32 narrowing products of C >= 512 on csrc/c1n.hip (operands split once on their way into LDS) or on
+    gemm.hip's in-register split"""
+    _lib.call("wfae_set_c1n", int(bool(on)))
+
+
+def set_c1rb(on):
+    """A/B switch: the bf16 1x1 forward / data gradient on csrc/c1rb.hip (register-direct) or on csrc/c1b.hip (LDS-tiled)"""
+    global _C1RB
+    _C1RB = bool(on)
+
+
+def set_c1b(on):
+    """A/B switch: bf16 1x1 forward / data gradient on csrc/c1b.hip or on the element-typed generic GEMM kernel"""
+    global _C1B
+    _C1B = bool(on)
+
+
+def set_c1w(on):
+    """A/B switch: the 1x1 weight gradients on csrc/c1w.hip or on gemm.hip"""
+    global _C1W
+    _C1W = bool(on)
+
+
+def c1r_bndx_on():
+    return _C1R_BNDX
+
+
+def c1n_enabled():
+    return bool(_lib.load().wfae_get_c1n())
+
+
+def _precision():
+    return _lib.load().wfae_get_matmul_precision()
+
+
+def c1r_supported(m, k, hw):
+    return _C1R and _SPLIT_GEMM and _precision() == 0 and bool(_lib.load().wfae_c1r_supported(int(m), int(k), int(hw)))
+
+
 def c1r_bnred_supported(m, k, hw):
-    return (_C1R and _C1R_BNRED and _SPLIT_GEMM and _lib.load().wfae_get_matmul_precision() == 0
+    return (_C1R and _C1R_BNRED and _SPLIT_GEMM and _precision() == 0
             and bool(_lib.load().wfae_c1r_bnred_supported(int(m), int(k), int(hw))))
+
+
+def c1rb_supported(m, k, hw):
+    return _C1RB and _precision() == 1 and bool(_lib.load().wfae_c1rb_supported(int(m), int(k), int(hw)))
+
+
+def c1b_supported(m, k, hw):
+    return _C1B and _precision() == 1 and bool(_lib.load().wfae_c1b_supported(int(m), int(k), int(hw)))
+
+
+def conv1x1_bnact_supported(x, cout):
+    """geometries wfae_conv1x1_fwd_bnact / wfae_conv1x1_bwd_weight_bnact serve (the library re-checks and refuses the rest); x: the
+    operand or its (N, Cin, H, W) shape"""
+    nb, cin, h, wd = getattr(x, "shape", x)
+    swapped = cin < cout and cin < 128          # the weight gradient then computes dW^T (N = Cout columns)
+    return (h * wd) % 4 == 0 and h * wd >= 16 and cin % 4 == 0 and (cout % 4 == 0 or not swapped)
+
+
+def conv1x1_route(op, m, k, hw, storage="f32", prologue=False, bias=False, residual="none"):
+    """The kernel family that serves one 1x1 product — the whole decision, from the switches, the matmul precision and the
+    library's wfae_*_supported predicates; no tensor is touched.  -> 'c1r' | 'c1rb' | 'c1b' | 'c1w' | 'gemm'.
+
+    op 'fwd' | 'dgrad' | 'wgrad'; (m, k): y[m] = A[m, k] x[k] — forward (Cout, Cin), data gradient (Cin, Cout), weight
+    gradient (Cout, Cin) of the convolution it belongs to; hw pixels per image; storage 'f32' | 'bf16' of the activations;
+    prologue: BatchNorm + GELU in the operand loader; bias; residual 'none' | 'ordinary' | 'broadcast'.
+
+    'gemm' covers the library's own hand-off to csrc/c1n.hip: inside wfae_conv1x1_fwd / _fwd_stats / _fwd_bnact (no bias,
+    no residual) and wfae_conv1x1_bwd_data, fp32 tensors at fp32 precision with the split GEMMs on, (M, K) = (128, 512) and
+    (256, 1024), unless set_c1n(False).
+
+    Weight gradients: c1w wherever wfae_c1w_supported — fp32 tensors at fp32 precision with the split GEMMs on, bf16-stored
+    tensors at 'medium'.
+
+    A bias, a broadcast residual or a residual on a product that does not widen (m <= k; the register-direct kernels add
+    one to widening products only) stay on gemm.hip.
+
+    fp32 tensors: c1r for every shape it serves (profiles/r04_kbench_c1r_variants.txt, r04_kbench_c1r_knobs.txt): at
+    C = 256 gemm.hip's kernels are bound by the fp32 MFMA instruction and c1r wins all four products (0.346 -> 0.31, 0.445 ->
+    0.30, 0.685 -> 0.49, 0.500 -> 0.40 - 0.45 ms); at C = 128 both are HBM-bound: c1r wins the forward launches, which carry a
+    BatchNorm + GELU prologue and / or a residual + BatchNorm-sum epilogue in the step (0.72 -> 0.65, 1.14 -> 1.02 ms), and
+    ties the two plain data gradients (0.54 - 0.59 vs 0.57 - 0.59 ms) — one kernel family per stage, and every form of a
+    shape on the same kernel keeps fused and unfused forms bit-identical.  The M-sliced shapes of the C >= 512 stages serve the
+    widening products in both directions (profiles/r04_kbench_c1r_sliced.txt).
+
+    bf16-stored tensors (profiles/r04_kbench_c1rb_vs_c1b.txt): c1rb wins or ties every form except the narrowing products of
+    C >= 256 with the BatchNorm + GELU prologue, which run on c1b: the M-sliced ones (C >= 512) evaluate the activation of the
+    whole operand again in every slice (0.163 -> 0.462 ms), and the prologue forms run one wave per SIMD (csrc/c1rb.hip,
+    wfae_c1rb_fwd: with two, repeat launches differed), where C = 256 takes 0.327 ms against c1b's 0.284 (C = 128: 0.477
+    against 0.536, kept).  That exception holds whatever set_c1b says: the switch is the A/B of the shapes c1rb does not serve.
+    The bf16 forms of conv1x1_fwd* / conv1x1_bwd_data are gemm.hip's own (c1b needs the planes of c1b_weights, which they do
+    not have); functional.py follows this route."""
+    if op == "wgrad":
+        ok = _C1W and _lib.load().wfae_c1w_supported(int(k), int(m), int(hw))
+        return "c1w" if ok and (_precision() == 1 if storage == "bf16" else (_precision() == 0 and _SPLIT_GEMM)) else "gemm"
+    if bias or residual == "broadcast" or (residual == "ordinary" and m <= k):
+        return "gemm"
+    if storage == "f32":
+        return "c1r" if c1r_supported(m, k, hw) else "gemm"
+    rb = c1rb_supported(m, k, hw)
+    if rb and not (prologue and m < k and k >= 256):
+        return "c1rb"
+    return "c1b" if (rb or c1b_supported(m, k, hw)) else "gemm"
+
+
+def conv1x1_dgrad_bn_route(m, k, hw, storage="f32"):
+    """How the data gradient (m, k) in front of a BatchNorm + GELU backward takes that backward along (C <= 256 widening
+    gradients on c1r): 'bndx' — c1r_bnred(store=False) for the sums, then c1r_bndx, which computes the product again and
+    applies the second pass in its epilogue, so dA is never stored; 'bnred' — c1r_bnred stores dA, bn_act_bwd_dx reads it;
+    None — the product of conv1x1_route('dgrad', ...) followed by bn_act_bwd."""
+    if storage == "f32" and c1r_bnred_supported(m, k, hw):
+        return "bndx" if _C1R_BNDX else "bnred"
+    return None
+
+
+_C1_PEAK = {"c1r": PEAK_BF16_MFMA / 6, "c1rb": PEAK_BF16_MFMA, "c1b": PEAK_BF16_MFMA, "gemm": None}   # None: _PEAK_OF
+
+
+def _c1_launch(fam, w, transposed, x, st=None, bias=None, res=None, res_broadcast=False, stats=False, label=None):
+    """y = A f(x) (+ bias) (+ res) on family `fam`: A = w (Cout, Cin) or, transposed, w^T (the data gradient) — for c1b the bf16
+    (M, K) plane of c1b_weights that is already A; f = the BatchNorm + GELU of `st` or nothing; stats: the epilogue also
+    reduces the BatchNorm sums of y.  -> (y, StatRows | None); gemm.hip reports no rows for shapes whose epilogue has no
+    sums (run bn_stats_train on y)."""
+    sfx, es = _chka(x, res)
+    nb, k, h, wd = x.shape
+    hw, n = h * wd, nb * h * wd
+    if fam == "c1b":
+        if not sfx or w.dtype != BF16 or not w.is_contiguous() or w.shape[1] != k:
+            raise _lib.WfaeError("c1b_fwd: bf16 activations and the contiguous (M, K) bf16 weight plane of c1b_weights")
+        m = w.shape[0]
+    else:
+        _chk(w, bias)
+        if fam != "gemm" and (fam == "c1rb") != bool(sfx):
+            raise _lib.WfaeError(f"{fam}: {'bf16-stored' if fam == 'c1rb' else 'fp32'} activations")
+        m = w.shape[1] if transposed else w.shape[0]
+    y = torch.empty((nb, m, h, wd), dtype=x.dtype, device=x.device)
+    by = es * n * (k + m) + w.element_size() * k * m + (0 if res is None else es * n * m)
+    ps, ph = (None, None) if st is None else (_p(st.scale), _p(st.shift))
+    label = label or ("wfae_conv1x1_bwd_data" if transposed else "wfae_conv1x1_fwd_bnact" if st is not None else "wfae_conv1x1_fwd")
+    part, rows, out = None, None, _NO_ROWS
+    if stats:     # the register-direct capacity is sized for the widest user of the shape
+        cap = 4 * ((n + 127) // 128) * m if fam == "gemm" else 2 * int(getattr(_lib.load(), f"wfae_{fam}_stat_rows")(m, k, nb, hw)) * m
+        part, rows, out = _rows_out(cap, x.device)
+    if fam in ("c1r", "c1rb"):
+        name, args = f"wfae_{fam}_fwd", (_p(w), *((1, m) if transposed else (k, 1)), _p(x), ps, ph, _p(res), _p(y), nb, k, m, hw, *out)
+    elif fam == "c1b":
+        name, args = "wfae_c1b_fwd", (_p(w), _p(x), ps, ph, _p(res), _p(y), nb, k, m, hw, *out)
+    elif transposed:
+        name, args = "wfae_conv1x1_bwd_data" + sfx, (_p(x), _p(w), _p(y), nb, m, k, hw)
+    else:
+        tail = (_p(w), _p(bias), _p(res), 0 if res_broadcast else m * hw, _p(y), nb, k, m, hw)
+        if sfx or st is not None:
+            name, args = "wfae_conv1x1_fwd" + (sfx or "_bnact"), (_p(x), ps, ph, *tail, *out)
+        else:
+            name, args = ("wfae_conv1x1_fwd_stats", (_p(x), *tail, *out)) if stats else ("wfae_conv1x1_fwd", (_p(x), *tail))
+    _call(name, 2 * n * k * m, by, *args, _stream(), label=label, peak=_C1_PEAK[fam])
+    if not stats:
+        return y, None
+    if fam == "gemm":
+        return y, (StatRows(part, rows.value) if rows.value > 0 else None)
+    return y, StatRows(part if fam == "c1b" else part[:2 * rows.value * m], rows.value)
+
+
+# the private names tests/ reach into, as questions to the route and calls onto the launch path
+def _c1r_take(m, k, hw, dgrad):
+    return conv1x1_route("dgrad" if dgrad else "fwd", m, k, hw) == "c1r"
+
+
+def _c1w_route(dy, x, sfx):
+    return conv1x1_route("wgrad", dy.shape[1], x.shape[1], dy.shape[2] * dy.shape[3], "bf16" if sfx else "f32") == "c1w"
+
+
+def _c1r(w, transposed, x, st, res, stats, label):
+    r = _c1_launch("c1r", w, transposed, x, st, None, res, False, stats, label)
+    return r if stats else r[0]
+
+
+def _c1_fwd(x, st, w, bias, res, res_broadcast, stats):
+    nb, cin, h, wd = x.shape
+    residual = "broadcast" if res_broadcast else "none" if res is None else "ordinary"
+    fam = "gemm" if x.dtype == BF16 else conv1x1_route("fwd", w.shape[0], cin, h * wd, "f32", st is not None, bias is not None, residual)
+    return _c1_launch(fam, w, False, x, st, bias, res, res_broadcast, stats)
+
+
+def conv1x1_fwd(x, w, bias=None, res=None, res_broadcast=False):
+    if res_broadcast and x.dtype == BF16:
+        raise _lib.WfaeError("conv1x1_fwd: the broadcast residual (pos_emb) belongs to an fp32 layer")
+    return _c1_fwd(x, None, w, bias, res, res_broadcast, False)[0]
+
+
+def conv1x1_fwd_stats(x, w, bias=None, res=None):
+    """conv1x1_fwd whose epilogue also reduces the per-channel sum / sum of squares of y (for the BatchNorm that
+    follows).  -> (y, StatRows | None); None = this shape is not served, run bn_stats_train on y."""
+    return _c1_fwd(x, None, w, bias, res, False, True)
+
+
+def conv1x1_fwd_bnact(x, st, w, bias=None, res=None, stats=False):
+    """conv1x1_fwd(bn_act_fwd(x, st, GELU), w): the activated tensor is rebuilt in the GEMM's operand loader and never
+    written (reference chain BN -> GELU -> Conv2d 1x1, pipeline/models/ae_64x8x8_lin.py:14-15).  stats=True: the
+    epilogue also reduces the BatchNorm sums of y -> (y, StatRows | None)"""
+    r = _c1_fwd(x, st, w, bias, res, False, stats)
+    return r if stats else r[0]
+
+
+def conv1x1_bwd_data(dy, w):
+    nb, cout, h, wd = dy.shape
+    fam = "gemm" if dy.dtype == BF16 else conv1x1_route("dgrad", w.shape[1], cout, h * wd)
+    return _c1_launch(fam, w, True, dy)[0]
+
+
+def c1rb_fwd(w, transposed, x, st=None, res=None, stats=False, label="wfae_c1b_fwd"):
+    """_c1_launch on csrc/c1rb.hip (y bf16; the fp32 weight itself is passed, the kernel rounds it into its LDS image)
+    -> y | (y, StatRows)"""
+    r = _c1_launch("c1rb", w, transposed, x, st, None, res, False, stats, label)
+    return r if stats else r[0]
+
+
+def c1b_weights(w):
+    """w (Cout, Cin[,1,1]) fp32 -> (Wb (Cout, Cin), Wtb (Cin, Cout)) bf16"""
+    _chk(w)
+    cout, cin = w.shape[0], w.shape[1]
+    Wb = torch.empty((cout, cin), dtype=BF16, device=w.device)
+    Wtb = torch.empty((cin, cout), dtype=BF16, device=w.device)
+    _call("wfae_c1b_weights", 0, 8 * w.numel(), _p(w), _p(Wb), _p(Wtb), cout, cin, _stream())
+    return Wb, Wtb
+
+
+def c1b_fwd(Wb, x, st=None, res=None, stats=False, label="wfae_c1b_fwd"):
+    """_c1_launch on csrc/c1b.hip; Wb (M, K) from c1b_weights -> y | (y, StatRows of y)"""
+    r = _c1_launch("c1b", Wb, False, x, st, None, res, False, stats, label)
+    return r if stats else r[0]
+
+
+def _c1_wgrad(dy, x, st, dw, accumulate):
+    """dw (Cout, Cin) (+)= dy . f(x)^T, f = the BatchNorm + GELU of `st` rebuilt in the loader, or nothing"""
+    sfx, es = _chka(dy, x)
+    _chk(dw)
+    nb, cout, h, wd = dy.shape
+    cin, n = x.shape[1], nb * h * wd
+    pro = (None, None) if st is None else (_p(st.scale), _p(st.shift))
+    peak = None
+    if conv1x1_route("wgrad", cout, cin, h * wd, "bf16" if sfx else "f32", st is not None) == "c1w":
+        name, peak = "wfae_c1w_bwd_weight" + sfx, PEAK_BF16_MFMA / (1 if sfx else 6)
+    elif sfx:
+        name = "wfae_conv1x1_bwd_weight_bf16"
+    else:
+        name, pro = ("wfae_conv1x1_bwd_weight", ()) if st is None else ("wfae_conv1x1_bwd_weight_bnact", pro)
+    ws = workspace()
+    _call(name, 2 * n * cin * cout, es * n * (cin + cout) + 4 * cin * cout, _p(dy), _p(x), *pro, _p(dw), nb, cin, cout, h * wd,
+          int(accumulate), ws.data_ptr(), ws.numel(), _stream(), peak=peak,
+          label="wfae_conv1x1_bwd_weight" if st is None else "wfae_conv1x1_bwd_weight_bnact")
+    return dw
+
+
+def conv1x1_bwd_weight(dy, x, dw, accumulate=False):
+    return _c1_wgrad(dy, x, None, dw, accumulate)
+
+
+def conv1x1_bwd_weight_bnact(dy, x, st, dw, accumulate=False):
+    """conv1x1_bwd_weight(dy, bn_act_fwd(x, st, GELU), dw) without the activated tensor in HBM"""
+    return _c1_wgrad(dy, x, st, dw, accumulate)
 
 
 def c1r_bnred(w, dt, x, st, store=True):
     """da = conv1x1_bwd_data(dt, w) on c1r with phase 1 of bn_act_bwd(da, x, ...) taken in the epilogue -> (da, StatRows of
     (sum dU, sum dU xhat)); finish with bn_act_bwd_from_rows, then bn_act_bwd_dx — or, with store=False (da is None: the sums
     alone), with c1r_bndx, which rebuilds da in its own registers"""
-    import ctypes
     _chk(w, dt, x)
     nb, k, h, wd = dt.shape
-    m = w.shape[1]
+    m, n = w.shape[1], nb * h * wd
     da = torch.empty((nb, m, h, wd), dtype=torch.float32, device=dt.device) if store else None
-    rows_n = int(_lib.load().wfae_c1r_stat_rows(m, k, nb, h * wd))
-    part = torch.empty(2 * rows_n * m, dtype=torch.float64, device=dt.device)
-    rows = ctypes.c_int(0)
-    n = nb * h * wd
-    _call("wfae_c1r_bnred", 2 * n * k * m, 4 * (n * (k + (2 if store else 1) * m) + k * m), _p(w), 1, m, _p(dt), _p(x), _p(st.scale), _p(st.shift),
-          _p(st.mean), _p(st.invstd), _p(da), nb, k, m, h * wd, part.data_ptr(), part.numel(),
-          ctypes.cast(ctypes.pointer(rows), ctypes.c_void_p), _stream(), label="wfae_conv1x1_bwd_data", peak=PEAK_BF16_MFMA / 6)
+    part, rows, out = _rows_out(2 * int(_lib.load().wfae_c1r_stat_rows(m, k, nb, h * wd)) * m, dt.device)
+    _call("wfae_c1r_bnred", 2 * n * k * m, 4 * (n * (k + (2 if store else 1) * m) + k * m), _p(w), 1, m, _p(dt), _p(x), _p(st.scale),
+          _p(st.shift), _p(st.mean), _p(st.invstd), _p(da), nb, k, m, h * wd, *out, _stream(), label="wfae_conv1x1_bwd_data",
+          peak=_C1_PEAK["c1r"])
     return da, StatRows(part[:2 * rows.value * m], rows.value)
 
 
@@ -313,340 +571,18 @@ def bn_act_bwd_dx(dy, x, gamma, st, res=None, act=1, training=True):
     return dx
 
 
-_C1R_BNDX = True   # A/B through set_c1r_bndx()
-
-
-def set_c1r_bndx(on):
-    """A/B switch: the second pass of the first BatchNorm's backward in the epilogue of a recomputed data gradient (c1r_bndx)
-    or as bn_act_bwd_dx over the stored one"""
-    global _C1R_BNDX
-    _C1R_BNDX = bool(on)
-
-
-def c1r_bndx_on():
-    return _C1R_BNDX
-
-
 def c1r_bndx(w, dt, x, gamma, st, res=None, training=True):
     """dx of  conv1x1(gelu(bn(x)), w)  given dt, second pass: da = conv1x1_bwd_data(dt, w) rebuilt in registers and
     bn_act_bwd_dx(da, x, ...) + res applied in the epilogue (after c1r_bnred(store=False) + bn_act_bwd_from_rows on this stream)"""
     _chk(w, dt, x, gamma, res)
     nb, k, h, wd = dt.shape
-    m = w.shape[1]
+    m, n = w.shape[1], nb * h * wd
     dx = torch.empty((nb, m, h, wd), dtype=torch.float32, device=dt.device)
     ws = workspace()
-    n = nb * h * wd
     _call("wfae_c1r_bndx", 2 * n * k * m, 4 * (n * (k + (3 if res is not None else 2) * m) + k * m), _p(w), 1, m, _p(dt), _p(x), _p(gamma),
           _p(st.scale), _p(st.shift), _p(st.mean), _p(st.invstd), ws.data_ptr(), _p(res), _p(dx), nb, k, m, h * wd, int(training),
-          _stream(), label="wfae_c1r_bndx", peak=PEAK_BF16_MFMA / 6)
+          _stream(), label="wfae_c1r_bndx", peak=_C1_PEAK["c1r"])
     return dx
-
-
-# csrc/c1n.hip: the narrowing products of the C >= 512 stages ((M, K) = (128, 512), (256, 1024)), routed inside the library
-# from wfae_conv1x1_fwd / _fwd_stats / _fwd_bnact (no bias, no residual) and wfae_conv1x1_bwd_data
-def set_c1n(on):
-    """A/B switch: those products on csrc/c1n.hip (operands split once on their way into LDS) or on gemm.hip's in-register split"""
-    _lib.call("wfae_set_c1n", int(bool(on)))
-
-
-def c1n_enabled():
-    return bool(_lib.load().wfae_get_c1n())
-
-
-# csrc/c1rb.hip: the same register-direct product on bf16-stored tensors ('medium'): every Bottleneck stage with HW % 128 == 0
-_C1RB = True   # A/B through set_c1rb()
-
-
-def set_c1rb(on):
-    """A/B switch: the bf16 1x1 forward / data gradient on csrc/c1rb.hip (register-direct) or on csrc/c1b.hip (LDS-tiled)"""
-    global _C1RB
-    _C1RB = bool(on)
-
-
-def c1rb_supported(m, k, hw):
-    return _C1RB and _lib.load().wfae_get_matmul_precision() == 1 and bool(_lib.load().wfae_c1rb_supported(int(m), int(k), int(hw)))
-
-
-def c1rb_take(m, k, hw, pro):
-    """route this bf16 product to c1rb?  Measured (profiles/r04_kbench_c1rb_vs_c1b.txt): it wins or ties every form except
-    the narrowing products of C >= 256 with the BatchNorm + GELU prologue, which stay on c1b: the M-sliced ones (C >= 512)
-    evaluate the activation of the whole operand again in every slice (0.163 -> 0.462 ms), and the prologue forms run one wave
-    per SIMD (csrc/c1rb.hip, wfae_c1rb_fwd: with two, repeat launches differed), where C = 256 takes 0.327 ms against c1b's
-    0.284 (C = 128: 0.477 against 0.536, kept)."""
-    if pro and m < k and k >= 256:
-        return False
-    return c1rb_supported(m, k, hw)
-
-
-def c1rb_fwd(w, transposed, x, st=None, res=None, stats=False, label="wfae_c1b_fwd"):
-    """y (bf16) = A f(x) (+ res) on bf16-stored activations: A = w (Cout, Cin) or, transposed, w^T (the data gradient); the
-    fp32 weight itself is passed (the kernel rounds it into its LDS image) -> y | (y, StatRows)"""
-    import ctypes
-    sfx, _ = _chka(x, res)
-    _chk(w)
-    if not sfx:
-        raise _lib.WfaeError("c1rb_fwd: bf16-stored activations")
-    nb, k, h, wd = x.shape
-    cout, cin = w.shape[0], w.shape[1]
-    m, sm, sk = (cin, 1, cin) if transposed else (cout, cin, 1)
-    y = torch.empty((nb, m, h, wd), dtype=BF16, device=x.device)
-    fl = 2 * nb * h * wd * k * m
-    by = 2 * nb * h * wd * (k + m) + 4 * k * m + (0 if res is None else 2 * nb * h * wd * m)
-    ps, ph = (None, None) if st is None else (_p(st.scale), _p(st.shift))
-    if not stats:
-        _call("wfae_c1rb_fwd", fl, by, _p(w), sm, sk, _p(x), ps, ph, _p(res), _p(y), nb, k, m, h * wd, None, 0, None, _stream(),
-              label=label, peak=PEAK_BF16_MFMA)
-        return y
-    rows_n = int(_lib.load().wfae_c1rb_stat_rows(m, k, nb, h * wd))
-    part = torch.empty(2 * rows_n * m, dtype=torch.float64, device=x.device)
-    rows = ctypes.c_int(0)
-    _call("wfae_c1rb_fwd", fl, by, _p(w), sm, sk, _p(x), ps, ph, _p(res), _p(y), nb, k, m, h * wd, part.data_ptr(), part.numel(),
-          ctypes.cast(ctypes.pointer(rows), ctypes.c_void_p), _stream(), label=label, peak=PEAK_BF16_MFMA)
-    return y, StatRows(part[:2 * rows.value * m], rows.value)
-
-
-# ----------------------------------------------------------------- 1x1 conv
-def _conv1x1_fwd_bf16(x, st, w, bias, res, stats):
-    """the merged bf16-storage entry point: optional BatchNorm + GELU prologue (st), optional BatchNorm sums (stats)"""
-    import ctypes
-    _chka(x, res)
-    _chk(w, bias)
-    nb, cin, h, wd = x.shape
-    cout = w.shape[0]
-    y = torch.empty((nb, cout, h, wd), dtype=BF16, device=x.device)
-    fl = 2 * nb * h * wd * cin * cout
-    by = 2 * nb * h * wd * (cin + cout) + 4 * cin * cout + (0 if res is None else 2 * nb * h * wd * cout)
-    ps, ph = (None, None) if st is None else (_p(st.scale), _p(st.shift))
-    label = "wfae_conv1x1_fwd" if st is None else "wfae_conv1x1_fwd_bnact"
-    if not stats:
-        _call("wfae_conv1x1_fwd_bf16", fl, by, _p(x), ps, ph, _p(w), _p(bias), _p(res), cout * h * wd, _p(y), nb, cin, cout, h * wd,
-              None, 0, None, _stream(), label=label)
-        return y
-    part, cap = _stat_rows_buffer(nb, h * wd, cout, x.device)
-    rows = ctypes.c_int(0)
-    _call("wfae_conv1x1_fwd_bf16", fl, by, _p(x), ps, ph, _p(w), _p(bias), _p(res), cout * h * wd, _p(y), nb, cin, cout, h * wd,
-          part.data_ptr(), cap, ctypes.cast(ctypes.pointer(rows), ctypes.c_void_p), _stream(), label=label)
-    return y, (StatRows(part, rows.value) if rows.value > 0 else None)
-
-
-def conv1x1_fwd(x, w, bias=None, res=None, res_broadcast=False):
-    if x.dtype == BF16:
-        if res_broadcast:
-            raise _lib.WfaeError("conv1x1_fwd: the broadcast residual (pos_emb) belongs to an fp32 layer")
-        return _conv1x1_fwd_bf16(x, None, w, bias, res, False)
-    _chk(x, w, bias, res)
-    nb, cin, h, wd = x.shape
-    cout = w.shape[0]
-    if bias is None and not res_broadcast and (res is None or cout > cin) and _c1r_take(cout, cin, h * wd, False):
-        return _c1r(w, False, x, None, res, False, "wfae_conv1x1_fwd")
-    y = torch.empty((nb, cout, h, wd), dtype=x.dtype, device=x.device)
-    stride = 0 if res_broadcast else cout * h * wd
-    _call("wfae_conv1x1_fwd", 2 * nb * h * wd * cin * cout, 4 * (nb * h * wd * (cin + cout) + cin * cout) + (0 if res is None else 4 * nb * h * wd * cout), _p(x), _p(w), _p(bias), _p(res), stride, _p(y), nb, cin, cout, h * wd, _stream())
-    return y
-
-
-class StatRows:
-    """partial BatchNorm sums written by a GEMM epilogue: `part` (float64) = sum[rows][C] ++ sumsq[rows][C]"""
-    __slots__ = ("part", "rows")
-
-    def __init__(self, part, rows):
-        self.part, self.rows = part, rows
-
-
-class StatParts:
-    """fp64 partial BatchNorm sums left by a producer kernel: `part` = [splits][C][2] doubles (sum, sum of squares)"""
-    __slots__ = ("part", "splits")
-
-    def __init__(self, part, splits):
-        self.part, self.splits = part, splits
-
-
-def _stat_rows_buffer(nb, hw, cout, device):
-    cap = 4 * ((nb * hw + 127) // 128) * cout
-    return torch.empty(cap, dtype=torch.float64, device=device), cap
-
-
-def conv1x1_fwd_stats(x, w, bias=None, res=None):
-    """conv1x1_fwd whose epilogue also reduces the per-channel sum / sum of squares of y (for the BatchNorm that
-    follows).  -> (y, StatRows | None); None = this shape is not served, run bn_stats_train on y."""
-    import ctypes
-    if x.dtype == BF16:
-        return _conv1x1_fwd_bf16(x, None, w, bias, res, True)
-    _chk(x, w, bias, res)
-    nb, cin, h, wd = x.shape
-    cout = w.shape[0]
-    if bias is None and (res is None or cout > cin) and _c1r_take(cout, cin, h * wd, False):
-        return _c1r(w, False, x, None, res, True, "wfae_conv1x1_fwd")
-    y = torch.empty((nb, cout, h, wd), dtype=x.dtype, device=x.device)
-    part, cap = _stat_rows_buffer(nb, h * wd, cout, x.device)
-    rows = ctypes.c_int(0)
-    _call("wfae_conv1x1_fwd_stats", 2 * nb * h * wd * cin * cout,
-          4 * (nb * h * wd * (cin + cout) + cin * cout) + (0 if res is None else 4 * nb * h * wd * cout),
-          _p(x), _p(w), _p(bias), _p(res), cout * h * wd, _p(y), nb, cin, cout, h * wd, part.data_ptr(), cap,
-          ctypes.cast(ctypes.pointer(rows), ctypes.c_void_p), _stream(), label="wfae_conv1x1_fwd")
-    return y, (StatRows(part, rows.value) if rows.value > 0 else None)
-
-
-def conv1x1_bnact_supported(x, cout):
-    """geometries wfae_conv1x1_fwd_bnact / wfae_conv1x1_bwd_weight_bnact serve (the library re-checks and refuses the rest)"""
-    nb, cin, h, wd = x.shape
-    swapped = cin < cout and cin < 128          # the weight gradient then computes dW^T (N = Cout columns)
-    return (h * wd) % 4 == 0 and h * wd >= 16 and cin % 4 == 0 and (cout % 4 == 0 or not swapped)
-
-
-def conv1x1_fwd_bnact(x, st, w, bias=None, res=None, stats=False):
-    """conv1x1_fwd(bn_act_fwd(x, st, GELU), w): the activated tensor is rebuilt in the GEMM's operand loader and never
-    written (reference chain BN -> GELU -> Conv2d 1x1, pipeline/models/ae_64x8x8_lin.py:14-15).  stats=True: the
-    epilogue also reduces the BatchNorm sums of y -> (y, StatRows | None)"""
-    import ctypes
-    if x.dtype == BF16:
-        return _conv1x1_fwd_bf16(x, st, w, bias, res, stats)
-    _chk(x, w, bias, res)
-    nb, cin, h, wd = x.shape
-    cout = w.shape[0]
-    if bias is None and (res is None or cout > cin) and _c1r_take(cout, cin, h * wd, False):
-        return _c1r(w, False, x, st, res, stats, "wfae_conv1x1_fwd_bnact")
-    y = torch.empty((nb, cout, h, wd), dtype=x.dtype, device=x.device)
-    fl = 2 * nb * h * wd * cin * cout
-    by = 4 * (nb * h * wd * (cin + cout) + cin * cout) + (0 if res is None else 4 * nb * h * wd * cout)
-    if not stats:
-        _call("wfae_conv1x1_fwd_bnact", fl, by, _p(x), _p(st.scale), _p(st.shift), _p(w), _p(bias), _p(res), cout * h * wd, _p(y),
-              nb, cin, cout, h * wd, None, 0, None, _stream())
-        return y
-    part, cap = _stat_rows_buffer(nb, h * wd, cout, x.device)
-    rows = ctypes.c_int(0)
-    _call("wfae_conv1x1_fwd_bnact", fl, by, _p(x), _p(st.scale), _p(st.shift), _p(w), _p(bias), _p(res), cout * h * wd, _p(y),
-          nb, cin, cout, h * wd, part.data_ptr(), cap, ctypes.cast(ctypes.pointer(rows), ctypes.c_void_p), _stream())
-    return y, (StatRows(part, rows.value) if rows.value > 0 else None)
-
-
-# weight gradients on csrc/c1w.hip (both operands as K-contiguous rows, no LDS transpose): fp32 tensors at fp32 precision with
-# the split GEMMs on, bf16-stored tensors at 'medium'
-_C1W = True   # A/B through set_c1w()
-
-
-def set_c1w(on):
-    global _C1W
-    _C1W = bool(on)
-
-
-def _c1w_route(dy, x, sfx):
-    nb, cout, h, wd = dy.shape
-    if not (_C1W and _lib.load().wfae_c1w_supported(x.shape[1], cout, h * wd)):
-        return False
-    prec = _lib.load().wfae_get_matmul_precision()
-    return prec == 1 if sfx else (prec == 0 and _SPLIT_GEMM)
-
-
-def _c1w(dy, x, st, dw, accumulate, sfx, es, label):
-    nb, cout, h, wd = dy.shape
-    cin = x.shape[1]
-    ws = workspace()
-    ps, ph = (None, None) if st is None else (_p(st.scale), _p(st.shift))
-    _call("wfae_c1w_bwd_weight" + sfx, 2 * nb * h * wd * cin * cout, es * nb * h * wd * (cin + cout) + 4 * cin * cout, _p(dy), _p(x),
-          ps, ph, _p(dw), nb, cin, cout, h * wd, int(accumulate), ws.data_ptr(), ws.numel(), _stream(), label=label,
-          peak=PEAK_BF16_MFMA / (1 if sfx else 6))
-    return dw
-
-
-def conv1x1_bwd_weight_bnact(dy, x, st, dw, accumulate=False):
-    """conv1x1_bwd_weight(dy, bn_act_fwd(x, st, GELU), dw) without the activated tensor in HBM"""
-    sfx, es = _chka(dy, x)
-    _chk(dw)
-    if _c1w_route(dy, x, sfx):
-        return _c1w(dy, x, st, dw, accumulate, sfx, es, "wfae_conv1x1_bwd_weight_bnact")
-    nb, cout, h, wd = dy.shape
-    cin = x.shape[1]
-    ws = workspace()
-    if sfx:
-        _call("wfae_conv1x1_bwd_weight_bf16", 2 * nb * h * wd * cin * cout, 2 * nb * h * wd * (cin + cout) + 4 * cin * cout, _p(dy),
-              _p(x), _p(st.scale), _p(st.shift), _p(dw), nb, cin, cout, h * wd, int(accumulate), ws.data_ptr(), ws.numel(),
-              _stream(), label="wfae_conv1x1_bwd_weight_bnact")
-        return dw
-    _call("wfae_conv1x1_bwd_weight_bnact", 2 * nb * h * wd * cin * cout, 4 * (nb * h * wd * (cin + cout) + cin * cout),
-          _p(dy), _p(x), _p(st.scale), _p(st.shift), _p(dw), nb, cin, cout, h * wd, int(accumulate), ws.data_ptr(),
-          ws.numel(), _stream())
-    return dw
-
-
-def conv1x1_bwd_data(dy, w):
-    sfx, es = _chka(dy)
-    _chk(w)
-    nb, cout, h, wd = dy.shape
-    cin = w.shape[1]
-    if not sfx and _c1r_take(cin, cout, h * wd, True):
-        return _c1r(w, True, dy, None, None, False, "wfae_conv1x1_bwd_data")
-    dx = torch.empty((nb, cin, h, wd), dtype=dy.dtype, device=dy.device)
-    _call("wfae_conv1x1_bwd_data" + sfx, 2 * nb * h * wd * cin * cout, es * nb * h * wd * (cin + cout) + 4 * cin * cout, _p(dy), _p(w),
-          _p(dx), nb, cin, cout, h * wd, _stream(), label="wfae_conv1x1_bwd_data")
-    return dx
-
-
-def conv1x1_bwd_weight(dy, x, dw, accumulate=False):
-    sfx, es = _chka(dy, x)
-    _chk(dw)
-    if _c1w_route(dy, x, sfx):
-        return _c1w(dy, x, None, dw, accumulate, sfx, es, "wfae_conv1x1_bwd_weight")
-    nb, cout, h, wd = dy.shape
-    cin = x.shape[1]
-    ws = workspace()
-    if sfx:
-        _call("wfae_conv1x1_bwd_weight_bf16", 2 * nb * h * wd * cin * cout, 2 * nb * h * wd * (cin + cout) + 4 * cin * cout, _p(dy),
-              _p(x), None, None, _p(dw), nb, cin, cout, h * wd, int(accumulate), ws.data_ptr(), ws.numel(), _stream(),
-              label="wfae_conv1x1_bwd_weight")
-        return dw
-    _call("wfae_conv1x1_bwd_weight", 2 * nb * h * wd * cin * cout, 4 * (nb * h * wd * (cin + cout) + cin * cout), _p(dy), _p(x), _p(dw), nb, cin, cout, h * wd, int(accumulate),
-              ws.data_ptr(), ws.numel(), _stream())
-    return dw
-
-
-# ---- bf16 storage: csrc/c1b.hip (no format change between HBM and the matrix core)
-_C1B = True   # A/B through set_c1b()
-
-
-def set_c1b(on):
-    """A/B switch: bf16 1x1 forward / data gradient on csrc/c1b.hip or on the element-typed generic GEMM kernel"""
-    global _C1B
-    _C1B = bool(on)
-
-
-def c1b_supported(m, k, hw):
-    return _C1B and _lib.load().wfae_get_matmul_precision() == 1 and bool(_lib.load().wfae_c1b_supported(int(m), int(k), int(hw)))
-
-
-def c1b_weights(w):
-    """w (Cout, Cin[,1,1]) fp32 -> (Wb (Cout, Cin), Wtb (Cin, Cout)) bf16"""
-    _chk(w)
-    cout, cin = w.shape[0], w.shape[1]
-    Wb = torch.empty((cout, cin), dtype=BF16, device=w.device)
-    Wtb = torch.empty((cin, cout), dtype=BF16, device=w.device)
-    _call("wfae_c1b_weights", 0, 8 * w.numel(), _p(w), _p(Wb), _p(Wtb), cout, cin, _stream())
-    return Wb, Wtb
-
-
-def c1b_fwd(Wb, x, st=None, res=None, stats=False, label="wfae_c1b_fwd"):
-    """y (bf16) = W f(x) (+ res) on bf16-stored activations; Wb (M, K) from c1b_weights; st: BnStats folded into the
-    operand loader (BatchNorm + GELU in front of the convolution); stats=True: -> (y, StatRows of y)"""
-    import ctypes
-    sfx, _ = _chka(x, res)
-    if not sfx or Wb.dtype != BF16 or not Wb.is_contiguous() or Wb.shape[1] != x.shape[1]:
-        raise _lib.WfaeError("c1b_fwd: bf16 activations and the contiguous (M, K) bf16 weight plane of c1b_weights")
-    nb, k, h, wd = x.shape
-    m = Wb.shape[0]
-    y = torch.empty((nb, m, h, wd), dtype=BF16, device=x.device)
-    fl = 2 * nb * h * wd * k * m
-    by = 2 * nb * h * wd * (k + m) + 2 * k * m + (0 if res is None else 2 * nb * h * wd * m)
-    ps, ph = (None, None) if st is None else (_p(st.scale), _p(st.shift))
-    if not stats:
-        _call("wfae_c1b_fwd", fl, by, _p(Wb), _p(x), ps, ph, _p(res), _p(y), nb, k, m, h * wd, None, 0, None, _stream(), label=label,
-              peak=PEAK_BF16_MFMA)
-        return y
-    rows_n = int(_lib.load().wfae_c1b_stat_rows(m, k, nb, h * wd))
-    part = torch.empty(2 * rows_n * m, dtype=torch.float64, device=x.device)
-    rows = ctypes.c_int(0)
-    _call("wfae_c1b_fwd", fl, by, _p(Wb), _p(x), ps, ph, _p(res), _p(y), nb, k, m, h * wd, part.data_ptr(), part.numel(),
-          ctypes.cast(ctypes.pointer(rows), ctypes.c_void_p), _stream(), label=label, peak=PEAK_BF16_MFMA)
-    return y, StatRows(part, rows.value)
 
 
 # ------------------------------------------------------------------- linear
@@ -740,7 +676,6 @@ class WinoPlan:
 
 
 def _query_plan(variant, key):
-    import ctypes
     out = (ctypes.c_int64 * 4)()
     rc = _lib.load().wfae_wino_sizes(variant, *key, ctypes.cast(out, ctypes.c_void_p))
     if rc != 0:
@@ -885,7 +820,6 @@ WINO_STATS_MIN_TILES = 256
 def wino_down(U, V, pl, stats=False, out_dtype=torch.float32):
     """lo = Out(U * V) stored as `out_dtype`; stats=True: -> (lo, StatParts of lo) — the output transform also reduces the
     BatchNorm sums"""
-    import ctypes
     M = _buf(pl.nM, V)
     lo = torch.empty((pl.nb, pl.clo, pl.hlo, pl.wlo), dtype=out_dtype, device=V.device)
     es = lo.element_size()
@@ -905,18 +839,14 @@ def wino_down(U, V, pl, stats=False, out_dtype=torch.float32):
         else:
             _call("wfae_wino_out", 0, 4 * (pl.nM + lo.numel()), pl.variant, _p(M), _p(lo), pl.nb, pl.clo, pl.hlo, pl.wlo, _stream())
         return (lo, None) if stats else lo
-    cap = 2 * pl.clo * pl.nb * (((pl.hlo // m) * (pl.wlo // m) + 255) // 256)
-    part = torch.empty(cap, dtype=torch.float64, device=V.device)
-    splits = ctypes.c_int(0)
+    part, splits, out = _rows_out(2 * pl.clo * pl.nb * (((pl.hlo // m) * (pl.wlo // m) + 255) // 256), V.device)
     _call("wfae_wino_out_bf16" if out_dtype == BF16 else "wfae_wino_out_stats", 0, 4 * pl.nM + es * lo.numel(), pl.variant, _p(M),
-          _p(lo), pl.nb, pl.clo, pl.hlo, pl.wlo, part.data_ptr(), cap, ctypes.cast(ctypes.pointer(splits), ctypes.c_void_p),
-          _stream(), label="wfae_wino_out")
+          _p(lo), pl.nb, pl.clo, pl.hlo, pl.wlo, *out, _stream(), label="wfae_wino_out")
     return lo, StatParts(part, splits.value)
 
 
 def wino_up(U, Mt, pl, stats=False, out_dtype=torch.float32):
     """hi = In^T(U^T * Mt) stored as `out_dtype`; stats=True: -> (hi, StatParts of hi)"""
-    import ctypes
     dV = _buf(pl.nV, Mt)
     hi = torch.empty((pl.nb, pl.chi, 2 * pl.hlo, 2 * pl.wlo), dtype=out_dtype, device=Mt.device)
     es = hi.element_size()
@@ -934,12 +864,9 @@ def wino_up(U, Mt, pl, stats=False, out_dtype=torch.float32):
         else:
             _call("wfae_wino_in_t", 0, 4 * (pl.nV + hi.numel()), pl.variant, _p(dV), _p(hi), pl.nb, pl.chi, pl.hlo, pl.wlo, _stream())
         return (hi, None) if stats else hi
-    cap = 2 * pl.chi * pl.nb * (((pl.hlo // m) * (pl.wlo // m) + 255) // 256)
-    part = torch.empty(cap, dtype=torch.float64, device=Mt.device)
-    splits = ctypes.c_int(0)
+    part, splits, out = _rows_out(2 * pl.chi * pl.nb * (((pl.hlo // m) * (pl.wlo // m) + 255) // 256), Mt.device)
     _call("wfae_wino_in_t_bf16" if out_dtype == BF16 else "wfae_wino_in_t_stats", 0, 4 * pl.nV + es * hi.numel(), pl.variant, _p(dV),
-          _p(hi), pl.nb, pl.chi, pl.hlo, pl.wlo, part.data_ptr(), cap, ctypes.cast(ctypes.pointer(splits), ctypes.c_void_p),
-          _stream(), label="wfae_wino_in_t")
+          _p(hi), pl.nb, pl.chi, pl.hlo, pl.wlo, *out, _stream(), label="wfae_wino_in_t")
     return hi, StatParts(part, splits.value)
 
 
@@ -1215,17 +1142,14 @@ def bn_stats_from_parts(sp, shape, gamma, beta, running_mean, running_var, eps=1
 
 def bn_act_fwd_stats(x, st, act=1):
     """bn_act_fwd that also reduces the BatchNorm sums of its OUTPUT -> (y, StatParts)"""
-    import ctypes
     sfx, es = _chka(x)
     nb, c, h, wd = x.shape
     y = torch.empty_like(x)
     # capacity for the library's LARGEST split count per (image, channel) — its scalar path, cdiv(HW, 1024) clamped to
     # 1..1024 (the 16-byte path, taken by pointer alignment as well as by shape, needs fewer); `splits` comes back from the call
-    cap = 2 * c * nb * max(1, min(1024, (h * wd + 1023) // 1024))
-    part = torch.empty(cap, dtype=torch.float64, device=x.device)
-    splits = ctypes.c_int(0)
+    part, splits, out = _rows_out(2 * c * nb * max(1, min(1024, (h * wd + 1023) // 1024)), x.device)
     _call("wfae_bn_act_fwd_stats" + sfx, 0, 2 * es * x.numel(), _p(x), _p(st.scale), _p(st.shift), _p(y), nb, c, h * wd, act,
-          part.data_ptr(), cap, ctypes.cast(ctypes.pointer(splits), ctypes.c_void_p), _stream(), label="wfae_bn_act_fwd")
+          *out, _stream(), label="wfae_bn_act_fwd")
     return y, StatParts(part, splits.value)
 
 
@@ -2039,7 +1963,6 @@ def skill_scores(pred, target, thresholds, pools, clamp01=False):
     floats (compared in fp32, like `tensor >= python_float`); pools: up to 3 (type, scale) pairs, type in
     'none' / 'avg' / 'max'.  -> int64 device tensor (len(pools), 3 * len(thresholds) + 2): per pool [tp, fn, fp] per
     threshold (on the ensemble mean), the CRPS sum over pooled cells as the bits of a float64, the pooled cell count."""
-    import ctypes
     _chk(pred, target)
     if pred.dim() == 5:
         b, t, c, h, w = pred.shape
