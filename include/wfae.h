@@ -198,6 +198,18 @@ int wfae_c1w_bwd_weight(const float* dy, const float* x, const float* bn_scale, 
                         int Cout, int HW, int accumulate, void* ws, size_t ws_bytes, wfae_stream_t stream);
 int wfae_c1w_bwd_weight_bf16(const uint16_t* dy, const uint16_t* x, const float* bn_scale, const float* bn_shift, float* dw, int NB,
                              int Cin, int Cout, int HW, int accumulate, void* ws, size_t ws_bytes, wfae_stream_t stream);
+/* The two products of a Bottleneck's backward pass that read the incoming gradient dy (NB,C,HW) at C = 128 / 256, mid = C / 4,
+ * in ONE pass over dy (csrc/c1wd.hip): dw3 (C,mid) (+)= dy . gelu(t2 * bn_scale[m] + bn_shift[m])^T — the result of
+ * wfae_c1w_bwd_weight on the same arguments, bit for bit — and da3 (NB,mid,HW) = w3^T dy — the result of wfae_c1r_fwd with the
+ * transposed weight, bit for bit.  fp32 tensors at fp32 precision with the split GEMMs on, HW % 64 == 0, dy and t2 16-byte
+ * aligned; ws as wfae_c1w_bwd_weight.  wfae_c1wd_supported: 1 when the shape is served and the switch is on
+ * (wfae_set_c1wd, on by default; environment WFAE_C1WD=0 turns it off at load) — otherwise wfae_c1wd_bwd returns
+ * WFAE_ERR_UNSUPPORTED and the caller runs the two launches.  Process-wide; read at launch. */
+int wfae_set_c1wd(int on);
+int wfae_get_c1wd(void);
+int wfae_c1wd_supported(int C, int mid, int HW);
+int wfae_c1wd_bwd(const float* dy, const float* t2, const float* bn_scale, const float* bn_shift, const float* w3, float* dw3,
+                  float* da3, int NB, int C, int mid, int HW, int accumulate, void* ws, size_t ws_bytes, wfae_stream_t stream);
 /* ---- nn.Linear (to_latent / from_latent, ae_64x8x8_lin.py:74-75,92,98) ---
  * y[b,o] = sum_i x[b,i] w[o,i] + bias[o] */
 int wfae_linear_fwd(const float* x, const float* w, const float* bias, float* y, int B, int In,

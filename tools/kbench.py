@@ -172,6 +172,34 @@ def main():
                             acc(f"c1n_{key}_{'new' if on else 'old'}_pass{rep}", ms, mult)
                 ops.set_c1n(True)
                 del x, w1, w3
+    if "c1wd" in only:
+        # csrc/c1wd.hip (dW3 and dA3 from one pass over dy) against the pair c1w + c1r, at the two flagship shapes and at the small
+        # sizes around the crossover of ops.C1WD_MIN_HW; two passes, pair and fused interleaved: the spread of the pair between
+        # its passes is the noise the gain is read against
+        st = None
+        for rep in range(-1, 2):     # pass -1 warms the clocks up and is not reported
+            for c, h, w_ in [(128, S, S), (256, S // 2, S // 2), (128, 96, 96), (128, 64, 64), (128, 32, 32), (128, 16, 32), (256, 96, 96),
+                             (256, 64, 64), (256, 32, 32), (256, 16, 32)]:
+                mid = c // 4
+                n = B * h * w_
+                dy, t2 = rnd(B, c, h, w_), rnd(B, mid, h, w_)
+                w3, dw = rnd(c, mid, 1, 1) * 0.1, torch.empty(c, mid, 1, 1, device=dev)
+                st = ops.BnStats(mid, dev)
+                st.scale.copy_(torch.rand(mid, device=dev) + 0.5)
+                st.shift.copy_(torch.rand(mid, device=dev) - 0.5)
+                assert ops.conv1x1_wd_supported(c, mid, h * w_)
+
+                def pair():
+                    ops.conv1x1_bwd_weight_bnact(dy, t2, st, dw)
+                    return ops.conv1x1_bwd_data(dy, w3)
+
+                fl, by_pair, by_fused = 4 * n * c * mid, 4 * n * (2 * c + 2 * mid), 4 * n * (c + 2 * mid)
+                for tag, fn, by in [("pair c1w + c1r", pair, by_pair), ("fused c1wd", lambda: ops.conv1x1_bwd_wd(dy, t2, st, w3, dw), by_fused)]:
+                    ms = timeit(fn, R)
+                    if rep >= 0:
+                        report(f"c1wd C {c} @{h}x{w_} {tag} pass{rep}", ms, fl, by)
+                        acc(f"c1wd_{c}_{h * w_}_{tag.split()[0]}_pass{rep}", ms)
+                del dy, t2, w3, dw
     if "bnseq" in only:
         # first BatchNorm of a Bottleneck, backward: data gradient of the C -> C/4 convolution + BatchNorm/GELU backward (+ residual
         # gradient), with the reduce pass separate or in the c1r epilogue (ops.set_c1r_bnred)

@@ -288,17 +288,8 @@ int c1w_impl(const T* dy, const T* x, const float* bn_scale, const float* bn_shi
   p.pro_scale = bn_scale;
   p.pro_shift = bn_shift;
   const size_t slab = (size_t)Cin * Cout * sizeof(float);
-  // K chunks per image: ~1024 blocks in flight, chunks of at least 256 pixels, slabs within the workspace
-  const int tiles = cdiv(p.MP, p.MP > 128 ? 256 : 128) * cdiv(p.MQ, p.MQ > 64 ? 128 : 64);
-  int cpi = cdiv(1024, (long)tiles * NB);
-  const int max_cpi = HW / 256 > 0 ? HW / 256 : 1;
-  if (cpi > max_cpi) cpi = max_cpi;
-  if (cpi < 1) cpi = 1;
-  while (cpi > 1 && (size_t)NB * cpi * slab > ws_bytes) --cpi;
-  WFAE_REQUIRE((size_t)NB * cpi * slab <= ws_bytes, WFAE_ERR_WORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, (size_t)NB * slab);
-  p.cpi = cpi;
-  p.kc = cdiv(cdiv(HW, cpi), WBK) * WBK;
-  p.cpi = cdiv(HW, p.kc);     // chunks that actually hold pixels
+  WFAE_REQUIRE(c1w_chunks(p.MP, p.MQ, NB, HW, ws_bytes, &p.cpi, &p.kc), WFAE_ERR_WORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes,
+               (size_t)NB * slab);
   p.slab = (float*)ws;
   int rc;
   const int pro = bn_scale ? (x_is_p ? 1 : 2) : 0;
@@ -311,6 +302,25 @@ int c1w_impl(const T* dy, const T* x, const float* bn_scale, const float* bn_shi
 }
 
 }  // namespace
+
+namespace wfae {
+
+// K chunks per image: ~1024 blocks in flight, chunks of at least 256 pixels, slabs within the workspace
+bool c1w_chunks(int MP, int MQ, int NB, int HW, size_t ws_bytes, int* cpi_out, int* kc_out) {
+  const size_t slab = (size_t)MP * MQ * sizeof(float);
+  const int tiles = cdiv(MP, MP > 128 ? 256 : 128) * cdiv(MQ, MQ > 64 ? 128 : 64);
+  int cpi = cdiv(1024, (long)tiles * NB);
+  const int max_cpi = HW / 256 > 0 ? HW / 256 : 1;
+  if (cpi > max_cpi) cpi = max_cpi;
+  if (cpi < 1) cpi = 1;
+  while (cpi > 1 && (size_t)NB * cpi * slab > ws_bytes) --cpi;
+  if ((size_t)NB * cpi * slab > ws_bytes) return false;
+  *kc_out = cdiv(cdiv(HW, cpi), WBK) * WBK;
+  *cpi_out = cdiv(HW, *kc_out);     // chunks that actually hold pixels
+  return true;
+}
+
+}  // namespace wfae
 
 extern "C" {
 

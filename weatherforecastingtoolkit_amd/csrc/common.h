@@ -280,6 +280,10 @@ int wino_weights_t(int variant, const float* dU, float* dw, int Clo, int Chi, in
 int c1n_launch(const float* w, bool transposed, const float* x, const float* scale, const float* shift, float* y, int NB, int K, int M,
                int HW, double* stat_part, int64_t stat_capacity, int* stat_rows, hipStream_t st, const char* what);
 
+// split-K geometry of the 1x1 weight gradients on c1w.hip (P rows MP >= Q rows MQ): chunks per image and pixels per chunk
+// (a multiple of 32); false: not even one slab per image fits the workspace.  c1wd.hip writes the same slabs.
+bool c1w_chunks(int MP, int MQ, int NB, int HW, size_t ws_bytes, int* cpi_out, int* kc_out);
+
 // out = (beta ? out : 0) + sum over `splits` partial slabs of MN floats (+ bias_n[i % N]); fixed order.
 int slab_reduce(const float* slab, float* out, const float* bias_n, long MN, int N, int splits, int beta,
                 hipStream_t st, int transpose_m = 0);

@@ -130,6 +130,16 @@ def _wgrad(fn, *tensors):
         join_side_stream()
 
 
+def _on_main(fn):
+    """run fn() (a launch that writes a gradient buffer) on the main stream — behind the side stream when grad_buffer handed
+    out a buffer autograd will add to an earlier contribution (see _wgrad)"""
+    if _force_main[0]:
+        _force_main[0] = False
+        if _overlap:
+            join_side_stream()
+    return fn()
+
+
 _arena_grads = [True]
 
 
@@ -656,12 +666,21 @@ class BottleneckFn(Function):
         dy = _c(dy)
         mid = w1.shape[0]
         dw3 = grad_buffer(w3)
+        da3 = None
         if a3.numel() == 0:     # a3 = gelu(bn3(t2)) was never materialised: rebuilt in the weight gradient's loader
-            _wgrad(lambda: ops.conv1x1_bwd_weight_bnact(dy, t2, st3, dw3), dy, t2, st3.scale, st3.shift)
+            if ops.conv1x1_wd_route(dy.shape[1], mid, dy.shape[2] * dy.shape[3], _storage(dy)) == "c1wd":
+                # dW3 and dA3 = W3^T dy in one pass over dy, on the main stream (the side stream only fills launch tails)
+                da3 = _on_main(lambda: ops.conv1x1_bwd_wd(dy, t2, st3, w3, dw3))
+            if da3 is None:
+                _wgrad(lambda: ops.conv1x1_bwd_weight_bnact(dy, t2, st3, dw3), dy, t2, st3.scale, st3.shift)
         else:
             _wgrad(lambda: ops.conv1x1_bwd_weight(dy, a3, dw3), dy, a3)
         dg3, db3 = grad_buffer(g3), grad_buffer(ctx.betas[2])
-        dt2 = _dgrad_bn(dy, w3, W3t, t2, g3, st3, dg3, db3, None, tr)
+        if da3 is not None:
+            dt2 = ops.bn_act_bwd(da3, t2, g3, st3, dg3, db3, None, 1, tr)
+        else:
+            dt2 = _dgrad_bn(dy, w3, W3t, t2, g3, st3, dg3, db3, None, tr)
+        del da3
         dwg = grad_buffer(wg)
         _wgrad(lambda: _g3_wgrad(dt2, a2, dwg, ctx.groups), dt2, a2)
         da2 = _g3_dgrad(dt2, wg, mid, ctx.groups)

@@ -275,6 +275,12 @@ def set_c1n(on):
     _lib.call("wfae_set_c1n", int(bool(on)))
 
 
+def set_c1wd(on):
+    """A/B switch: the last 1x1 weight gradient and the data gradient in front of the third BatchNorm of a C <= 256 Bottleneck in
+    one pass over dy (csrc/c1wd.hip) or as the pair c1w + c1r"""
+    _lib.call("wfae_set_c1wd", int(bool(on)))
+
+
 def set_c1rb(on):
     """A/B switch: the bf16 1x1 forward / data gradient on csrc/c1rb.hip (register-direct) or on csrc/c1b.hip (LDS-tiled)"""
     global _C1RB
@@ -299,6 +305,10 @@ def c1r_bndx_on():
 
 def c1n_enabled():
     return bool(_lib.load().wfae_get_c1n())
+
+
+def c1wd_enabled():
+    return bool(_lib.load().wfae_get_c1wd())
 
 
 def _precision():
@@ -532,6 +542,53 @@ def conv1x1_bwd_weight(dy, x, dw, accumulate=False):
 def conv1x1_bwd_weight_bnact(dy, x, st, dw, accumulate=False):
     """conv1x1_bwd_weight(dy, bn_act_fwd(x, st, GELU), dw) without the activated tensor in HBM"""
     return _c1_wgrad(dy, x, st, dw, accumulate)
+
+
+# Pixels per image from which the Bottleneck backward takes the fused form.  No crossover was found: tools/kbench.py --only c1wd
+# (profiles/r08_c1wd_kbench_vs_pair.txt, B = 32) has the fused launch ahead at every size measured, down to 512 pixels, the
+# smallest — 0.036 -> 0.027 ms at C = 128, 0.053 -> 0.041 ms at C = 256, where it is one kernel + reduce against two kernels +
+# reduce.  Nothing below 512 was measured, and the launch traces recorded at 128 and 192 pixels
+# (tests/golden/g19_c1_launches.json) hold the pair.
+C1WD_MIN_HW = 512
+
+
+def conv1x1_wd_supported(c, mid, hw, storage="f32"):
+    """csrc/c1wd.hip serves the shape AND the two launches it replaces are today's pair (c1w weight gradient with the BatchNorm +
+    GELU prologue, c1r data gradient), whose results it reproduces bit for bit: C in (128, 256), mid = C / 4, hw % 64 == 0, fp32
+    tensors at fp32 precision with the split GEMMs on, set_c1wd / set_c1w / set_c1r on"""
+    return (storage == "f32" and _SPLIT_GEMM and _precision() == 0 and bool(_lib.load().wfae_c1wd_supported(int(c), int(mid), int(hw)))
+            and conv1x1_route("wgrad", c, mid, hw, "f32", True) == "c1w" and conv1x1_route("dgrad", mid, c, hw) == "c1r")
+
+
+def conv1x1_wd_route(c, mid, hw, storage="f32"):
+    """How a Bottleneck's backward computes dW3 and dA3 from dy when a3 was not materialised: 'c1wd' — one launch that reads dy
+    once (conv1x1_bwd_wd) — or 'pair' — conv1x1_bwd_weight_bnact + the data gradient of conv1x1_route.  Below C1WD_MIN_HW
+    pixels both forms are launch-bound and there is no dy traffic to save."""
+    return "c1wd" if hw >= C1WD_MIN_HW and conv1x1_wd_supported(c, mid, hw, storage) else "pair"
+
+
+def conv1x1_bwd_wd(dy, t2, st, w3, dw3, accumulate=False):
+    """dw3 (+)= dy . gelu(bn(t2))^T as conv1x1_bwd_weight_bnact(dy, t2, st, dw3) and da3 = w3^T dy as the c1r data gradient, both
+    bit for bit, in one pass over dy (csrc/c1wd.hip) -> da3; None: not served (nothing launched, the caller runs the pair) —
+    st None (the activated tensor was materialised), bf16-stored tensors, other shapes, set_c1wd(False)"""
+    if st is None or dy.dtype != torch.float32 or t2.dtype != torch.float32:
+        return None
+    nb, c, h, wd = dy.shape
+    mid, hw = t2.shape[1], h * wd
+    if not conv1x1_wd_supported(c, mid, hw):
+        return None
+    _chk(dy, t2, w3, dw3)
+    if tuple(t2.shape) != (nb, mid, h, wd) or w3.numel() != c * mid or dw3.numel() != c * mid:
+        raise _lib.WfaeError("conv1x1_bwd_wd: dy (N, C, H, W), t2 (N, C/4, H, W), w3 and dw3 (C, C/4)")
+    if (dy.data_ptr() | t2.data_ptr()) & 15:
+        return None
+    da = torch.empty_like(t2)
+    n = nb * hw
+    ws = workspace()
+    _call("wfae_c1wd_bwd", 4 * n * c * mid, 4 * n * (c + 2 * mid) + 8 * c * mid, _p(dy), _p(t2), _p(st.scale), _p(st.shift), _p(w3),
+          _p(dw3), _p(da), nb, c, mid, hw, int(accumulate), ws.data_ptr(), ws.numel(), _stream(), peak=PEAK_BF16_MFMA / 6,
+          label="wfae_c1wd_bwd")
+    return da
 
 
 def c1r_bnred(w, dt, x, st, store=True):
