@@ -646,7 +646,7 @@ int wfae_huber_fwd(const float* pred, const float* target, float* loss, int64_t 
 int wfae_huber_bwd(const float* pred, const float* target, const float* gloss, float* dpred, int64_t n, float delta,
                    wfae_stream_t stream);
 
-/* ---- frozen AutoencoderKL latent provider, forward only (reference pipeline/models/autoencoderkl/autoencoder_kl.py
+/* ---- AutoencoderKL forward: the frozen latent provider, and the forward of training (backward: the block below) (reference pipeline/models/autoencoderkl/autoencoder_kl.py
  * `AutoencoderKL`; vae.py `Encoder`, `Decoder`; resnet.py `ResnetBlock2D`, `Downsample2D`, `Upsample2D`; attention.py
  * `AttentionBlock`; distributions.py `DiagonalGaussianDistribution`).  Added within ABI version 103; nothing changed.
  * conv3: 3x3 convolution, NCHW fp32, implicit GEMM on the matrix cores with fp32 accumulation.
@@ -684,6 +684,45 @@ int wfae_aekl_from_tokens(const float* tok, const float* res, float* y, int N, i
 int wfae_aekl_softmax(const float* x, float* y, int64_t rows, int cols, float scale, wfae_stream_t stream);
 int wfae_aekl_posterior(const float* moments, const float* noise, float* mean, float* logvar, float* std_, float* sample, int N,
                         int C, int HW, wfae_stream_t stream);
+
+/* ---- AutoencoderKL backward (csrc/aekl_bwd.hip): what `AutoencoderKL.unfreeze()` trains with.  NCHW fp32, fixed summation
+ * order, no atomics: two launches give the same bits.  Added within ABI version 103; nothing changed.
+ * kind, mode, N, Cin, Cout, H, W are those of the wfae_aekl_conv3_fwd call being differentiated (x (N, Cin, H, W),
+ * dy (N, Cout, Ho, Wo)), with its range checks.
+ * conv3_bwd_data: du (N, Cin, H, W) = conv(dy, w rotated 180 degrees, in / out transposed) * silu'(x * scale + shift),
+ *   silu'(u) = s (1 + u (1 - s)), s = sigmoid(u): the gradient of the forward prologue's pre-activation.  Null gn_scale /
+ *   gn_shift (both or neither): no factor, x may be null.  packed_t: w.flip(2, 3).transpose(0, 1) (Cin, Cout, 3, 3) packed
+ *   with wfae_aekl_conv3_pack(wt, packed_t, Cin, Cout, mode).  kind 1 reads dy through zero insertion; kind 2 runs on the
+ *   2H x 2W grid and adds up each 2 x 2 block in the epilogue (no 4x tensor).  Modes 1, 3, 4.
+ * conv3_bwd_weight: dw (Cout, Cin, 3, 3) = sum over samples and output pixels of dy * a, a = SiLU(x * scale + shift)
+ *   recomputed on the load (null scale / shift: a = x), padding taps zero after it; written, not accumulated.  dbias (Cout,
+ *   may be null) = sum of dy.  On v_mfma_f32_16x16x32_bf16 with the pixels as K: mode 3 exact three-plane operands, mode 1
+ *   operands rounded to bf16 after the prologue, mode 4 WFAE_ERR_UNSUPPORTED.  The pixel reduction is split by sample and
+ *   by groups of 8 pixel tiles into slabs of ws (>= conv3_wgrad_ws_bytes, 16-byte aligned) that a finalize launch adds in
+ *   ascending order.
+ * gn_bwd: GroupNorm backward.  du (N, C, HW) is the gradient of u = gamma xhat + beta, xhat = (x - mean) rstd with
+ *   mean / rstd (N, groups) from gn_stats.  s1 = sum du gamma_c, s2 = sum du gamma_c xhat per (sample, group),
+ *   m = C / groups * HW:  dx = rstd (du gamma_c - (s1 + xhat s2) / m) + skip (dx's shape, may be null: the gradient
+ *   arriving on the residual path);  dbeta[c] = sum du, dgamma[c] = sum du xhat over samples and pixels (fp64 partials,
+ *   written, not accumulated).  ws >= gn_bwd_ws_bytes, 8-byte aligned; N * C <= 65535.
+ * softmax_bwd: ds[row] = p (dp - sum_j p_j dp_j) scale for y = softmax(scale * x) (in place over dp allowed).
+ * posterior_bwd: dmoments (N, 2C, HW) from dz (N, C, HW; may be null), the noise of the sample (null: z was the mean), the
+ *   raw moments and gkl (N; may be null), the gradient of each sample's KL 0.5 sum(mean^2 + var - 1 - logvar):
+ *   dmean = dz + gkl mean;  dlogvar = (0.5 dz noise std + 0.5 gkl (var - 1)) * [-30 <= raw logvar <= 20] (inclusive, as
+ *   torch.clamp's gradient). */
+int wfae_aekl_conv3_bwd_data(const float* dy, const void* packed_t, const float* x, const float* gn_scale, const float* gn_shift,
+                             float* du, int kind, int mode, int N, int Cin, int Cout, int H, int W, wfae_stream_t stream);
+size_t wfae_aekl_conv3_wgrad_ws_bytes(int kind, int N, int Cin, int Cout, int H, int W);
+int wfae_aekl_conv3_bwd_weight(const float* dy, const float* x, const float* gn_scale, const float* gn_shift, float* dw,
+                               float* dbias, int kind, int mode, int N, int Cin, int Cout, int H, int W, void* ws,
+                               size_t ws_bytes, wfae_stream_t stream);
+size_t wfae_aekl_gn_bwd_ws_bytes(int N, int C, int groups);
+int wfae_aekl_gn_bwd(const float* du, const float* x, const float* gamma, const float* mean, const float* rstd, const float* skip,
+                     float* dx, float* dgamma, float* dbeta, int N, int C, int HW, int groups, void* ws, size_t ws_bytes,
+                     wfae_stream_t stream);
+int wfae_aekl_softmax_bwd(const float* p, const float* dp, float* ds, int64_t rows, int cols, float scale, wfae_stream_t stream);
+int wfae_aekl_posterior_bwd(const float* dz, const float* noise, const float* moments, const float* gkl, float* dmoments, int N,
+                            int C, int HW, wfae_stream_t stream);
 
 /* ---- LPIPS perceptual loss of the AE+GAN step (reference pipeline/models/autoencoderkl/losses/lpips.py `LPIPS`,
  * `ScalingLayer`, `vgg16`, `normalize_tensor`, `spatial_average`; used by experiments/ae_v2_2/train.py:56-60): forward and

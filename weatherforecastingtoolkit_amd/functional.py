@@ -1403,6 +1403,143 @@ def aekl_posterior(moments, noise=None):
     return ops.aekl_posterior(_c(moments.detach()), None if noise is None else _c(noise))
 
 
+# ---- AutoencoderKL training (csrc/aekl_bwd.hip): the autograd Functions behind `AutoencoderKL.unfreeze()`.  They save
+# inputs and statistics, never an activated tensor, keep nothing that a backward consumes, and so run a second backward
+# under retain_graph (the adaptive weight of the KL-GAN loss differentiates twice before backward).
+class AeklConv3Fn(Function):
+    """(conv3x3(SiLU(GroupNorm(x))) + bias + res) * out_mul on ops.aekl_conv3_fwd; `norm` None: the plain convolution.
+    `conv` is the pipeline's Conv3x3: it owns the packed weights of both orientations."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, gamma, beta, res, conv, norm, kind, out_mul, mode):
+        x = _c(x)
+        gn = mean = rstd = None
+        if norm is not None:
+            mean, rstd, scale, shift = ops.aekl_gn_stats(x, gamma, beta, norm.num_groups, norm.eps)
+            gn = (scale, shift)
+        y = ops.aekl_conv3_fwd(x, conv.packed(mode), w.shape[0], bias, gn, None if res is None else _c(res), kind, mode, out_mul)
+        ctx.save_for_backward(x, w, gamma, mean, rstd, *(gn or ()))
+        ctx.conv, ctx.bias, ctx.has_res, ctx.kind, ctx.out_mul, ctx.mode = conv, bias, res is not None, kind, out_mul, mode
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, gamma, mean, rstd, *gn = ctx.saved_tensors
+        gn = tuple(gn) if gn else None
+        dy = _c(dy)
+        if ctx.out_mul != 1.0:
+            dy = dy * ctx.out_mul
+        dw, dbias = grad_buffer(w), None if ctx.bias is None else grad_buffer(ctx.bias)
+        ops.aekl_conv3_bwd_weight(dy, x, dw, dbias, gn, ctx.kind, ctx.mode)
+        dx = dgamma = dbeta = None
+        if gn is not None or ctx.needs_input_grad[0]:
+            dx = ops.aekl_conv3_bwd_data(dy, ctx.conv.packed_t(ctx.mode), x, gn, ctx.kind, ctx.mode)
+        if gn is not None:
+            dx, dgamma, dbeta = ops.aekl_gn_bwd(dx, x, gamma, mean, rstd)
+        return dx, dw, dbias, dgamma, dbeta, (dy if ctx.has_res else None), None, None, None, None, None
+
+
+def aekl_conv3x3_train(x, conv, norm=None, res=None, kind=0, out_mul=1.0, mode=None):
+    mode = ops.aekl_mode() if mode is None else mode
+    gamma, beta = (norm.weight, norm.bias) if norm is not None else (None, None)
+    return AeklConv3Fn.apply(x, conv.weight, conv.bias, gamma, beta, res, conv, norm, int(kind), float(out_mul), mode)
+
+
+class AeklAttentionFn(Function):
+    """the single-head AttentionBlock of aekl_attention with its GroupNorm, differentiable: the five products of the backward
+    run on linear_bwd_data / linear_bwd_weight / split_gemm, the transposes on the token kernels"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, wq, bq, wk, bk, wv, bv, wo, bo, groups, eps, rescale):
+        x = _c(x)
+        n, c, h, w = x.shape
+        s = h * w
+        planes = 1 if ops.get_float32_matmul_precision() == "medium" else 3
+        mean, rstd, scale, shift = ops.aekl_gn_stats(x, gamma, beta, groups, eps)
+        tok = ops.aekl_to_tokens(x, (scale, shift)).view(n * s, c)
+        q = ops.linear_fwd(tok, wq, bq).view(n, s, c)
+        k = ops.linear_fwd(tok, wk, bk).view(n, s, c)
+        v = ops.linear_fwd(tok, wv, bv).view(n, s, c)
+        scores = ops.split_gemm(ops.split_bf16x3(q, planes), ops.split_bf16x3(k, planes), b_kind=1)
+        probs = ops.aekl_softmax(scores, 1.0 / float(c) ** 0.5)
+        ctxv = ops.split_gemm(ops.split_bf16x3(probs, planes), ops.split_bf16x3(v, planes), b_kind=0)
+        out = ops.linear_fwd(ctxv.view(n * s, c), wo, bo).view(n, s, c)
+        ctx.save_for_backward(x, gamma, mean, rstd, tok, q, k, v, probs, ctxv, wq, wk, wv, wo)
+        ctx.biases, ctx.rescale, ctx.planes = (bq, bk, bv, bo), rescale, planes
+        return ops.aekl_from_tokens(out, x.shape, x, 1.0 / float(rescale))
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, mean, rstd, tok, q, k, v, probs, ctxv, wq, wk, wv, wo = ctx.saved_tensors
+        n, c, h, w = x.shape
+        s, planes = h * w, ctx.planes
+        dy = _c(dy)
+        if ctx.rescale != 1.0:
+            dy = dy * (1.0 / float(ctx.rescale))
+        sp = lambda t: ops.split_bf16x3(_c(t), planes)
+
+        def lin_bwd(d, inp, wt, b):
+            dwt = grad_buffer(wt)
+            ops.linear_bwd_weight(d, inp, dwt)
+            db = grad_buffer(b)
+            ops.reduce_sum(d, d.shape[0], wt.shape[0], 1, db)
+            return ops.linear_bwd_data(d, wt), dwt, db
+
+        dout = ops.aekl_to_tokens(dy).view(n * s, c)
+        dctx, dwo, dbo = lin_bwd(dout, ctxv.view(n * s, c), wo, ctx.biases[3])
+        dctx3 = sp(dctx.view(n, s, c))
+        dprobs = ops.split_gemm(dctx3, sp(v), b_kind=1)                                # (n, s_q, s_k)
+        dv = ops.split_gemm(sp(ops.aekl_to_tokens(probs)), dctx3, b_kind=0)            # probs^T dctx
+        ds = ops.aekl_softmax_bwd(probs, dprobs, 1.0 / float(c) ** 0.5)
+        dq = ops.split_gemm(sp(ds), sp(k), b_kind=0)
+        dk = ops.split_gemm(sp(ops.aekl_to_tokens(ds)), sp(q), b_kind=0)               # ds^T q
+        dtq, dwq, dbq = lin_bwd(dq.view(n * s, c), tok, wq, ctx.biases[0])
+        dtk, dwk, dbk = lin_bwd(dk.view(n * s, c), tok, wk, ctx.biases[1])
+        dtv, dwv, dbv = lin_bwd(dv.view(n * s, c), tok, wv, ctx.biases[2])
+        dtok = (dtq + dtk + dtv).view(n, s, c)
+        du = ops.aekl_from_tokens(dtok, x.shape)
+        dx, dgamma, dbeta = ops.aekl_gn_bwd(du, x, gamma, mean, rstd, skip=dy)         # skip: the residual path
+        return dx, dgamma, dbeta, dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo, None, None, None
+
+
+def aekl_attention_train(x, norm, q, k, v, o, rescale=1.0):
+    return AeklAttentionFn.apply(x, norm.weight, norm.bias, q.weight, q.bias, k.weight, k.bias, v.weight, v.bias, o.weight,
+                                 o.bias, int(norm.num_groups), float(norm.eps), float(rescale))
+
+
+class AeklPosteriorSampleFn(Function):
+    """z = mean + std * noise of the moments (noise None: the mean, `mode()`)"""
+
+    @staticmethod
+    def forward(ctx, moments, noise):
+        moments = _c(moments)
+        noise = None if noise is None else _c(noise)
+        mean, _, _, sample = ops.aekl_posterior(moments, noise)
+        ctx.save_for_backward(moments, *(() if noise is None else (noise,)))
+        return mean if noise is None else sample
+
+    @staticmethod
+    def backward(ctx, dz):
+        moments, *noise = ctx.saved_tensors
+        return ops.aekl_posterior_bwd(moments, _c(dz), noise[0] if noise else None), None
+
+
+class AeklPosteriorKlFn(Function):
+    """kl (N) = 0.5 sum(mean^2 + var - 1 - logvar) per sample"""
+
+    @staticmethod
+    def forward(ctx, moments):
+        moments = _c(moments)
+        mean, logvar, std, _ = ops.aekl_posterior(moments)
+        ctx.save_for_backward(moments)
+        return 0.5 * torch.sum(mean * mean + std * std - 1.0 - logvar, dim=[1, 2, 3])
+
+    @staticmethod
+    def backward(ctx, gkl):
+        moments, = ctx.saved_tensors
+        return ops.aekl_posterior_bwd(moments, gkl=_c(gkl))
+
+
 # ---- LPIPS perceptual loss (csrc/lpips.hip; reference pipeline/models/autoencoderkl/losses/lpips.py:47-60,107-129)
 LPIPS_SLICES = (2, 2, 3, 3, 3)   # 3x3 conv + ReLU layers per VGG16 slice; a 2 x 2 max-pool opens slices 2..5; a tap closes each
 

@@ -1852,6 +1852,109 @@ def aekl_posterior(moments, noise=None):
     return mean, logvar, std, sample
 
 
+# ---- AutoencoderKL backward (include/wfae.h "AutoencoderKL backward"; csrc/aekl_bwd.hip)
+def _aekl_out_plane(kind, h, wd):
+    return (h, wd) if kind == 0 else ((h - 2) // 2 + 1, (wd - 2) // 2 + 1) if kind == 1 else (2 * h, 2 * wd)
+
+
+def _aekl_bwd_args(what, dy, x_shape, kind, gn):
+    scale, shift = gn if gn is not None else (None, None)
+    if dy.dim() != 4 or len(x_shape) != 4 or kind not in (0, 1, 2):
+        raise _lib.WfaeError(f"{what}: expected dy (N, Cout, Ho, Wo), the shape of x (N, Cin, H, W) and kind 0, 1 or 2")
+    n, cin, h, wd = x_shape
+    if kind == 1 and (h < 2 or wd < 2):
+        raise _lib.WfaeError(f"{what}: the stride-2 form needs a plane of at least 2x2, got {h}x{wd}")
+    ho, wo = _aekl_out_plane(kind, h, wd)
+    if dy.shape[0] != n or tuple(dy.shape[2:]) != (ho, wo):
+        raise _lib.WfaeError(f"{what}: dy {tuple(dy.shape)} does not belong to x {tuple(x_shape)} and kind {kind}")
+    if gn is not None and (tuple(scale.shape) != (n, cin) or tuple(shift.shape) != (n, cin)):
+        raise _lib.WfaeError(f"{what}: prologue scale / shift {tuple(scale.shape)}, expected {(n, cin)}")
+    return scale, shift, n, cin, dy.shape[1], h, wd, ho, wo
+
+
+def aekl_conv3_bwd_data(dy, packed_t, x, gn=None, kind=0, mode=None, x_shape=None):
+    """du (x's shape) = conv(dy, rotated / transposed weights) * silu'(x * scale + shift) for gn = (scale, shift), the
+    gradient of the forward prologue's pre-activation; gn None: the plain data gradient (x may be None, give x_shape).
+    packed_t = aekl_conv3_pack(w.flip(2, 3).transpose(0, 1), mode)"""
+    mode = aekl_mode() if mode is None else mode
+    x_shape = tuple(x.shape) if x is not None else tuple(x_shape)
+    scale, shift, n, cin, cout, h, wd, ho, wo = _aekl_bwd_args("aekl_conv3_bwd_data", dy, x_shape, kind, gn)
+    _chk(dy, x, scale, shift)
+    if gn is not None and x is None:
+        raise _lib.WfaeError("aekl_conv3_bwd_data: the prologue factor needs x")
+    want = _lib.load().wfae_aekl_conv3_pack_bytes(cin, cout, mode)
+    if want == 0 or packed_t.dtype != torch.uint8 or packed_t.numel() != want or not packed_t.is_cuda:
+        raise _lib.WfaeError(f"aekl_conv3_bwd_data: packed weights do not belong to (Cin={cin}, Cout={cout}, 3, 3) mode={mode}")
+    du = torch.empty(x_shape, dtype=torch.float32, device=dy.device)
+    hg, wg = (2 * h, 2 * wd) if kind == 2 else (h, wd)
+    _call("wfae_aekl_conv3_bwd_data", 2 * 9 * n * hg * wg * cin * cout, 4 * (dy.numel() + du.numel() * (2 if gn else 1)) + want,
+          _p(dy), packed_t.data_ptr(), _p(x), _p(scale), _p(shift), _p(du), kind, mode, n, cin, cout, h, wd, _stream(),
+          label=f"wfae_aekl_conv3_bwd_data k{kind} {cout}->{cin} {ho}x{wo}", peak=_aekl_peak(mode))
+    return du
+
+
+def aekl_conv3_bwd_weight(dy, x, dw, dbias=None, gn=None, kind=0, mode=None):
+    """dw (Cout, Cin, 3, 3) = the weight gradient of aekl_conv3_fwd(x, ., gn=gn, kind=kind) under dy, the operand
+    SiLU(x * scale + shift) recomputed on the load; dbias (Cout) = sum of dy.  Both written, not accumulated."""
+    mode = aekl_mode() if mode is None else mode
+    scale, shift, n, cin, cout, h, wd, ho, wo = _aekl_bwd_args("aekl_conv3_bwd_weight", dy, tuple(x.shape), kind, gn)
+    _chk(dy, x, scale, shift, dw, dbias)
+    if tuple(dw.shape) != (cout, cin, 3, 3) or (dbias is not None and tuple(dbias.shape) != (cout,)):
+        raise _lib.WfaeError(f"aekl_conv3_bwd_weight: dw {tuple(dw.shape)}, expected {(cout, cin, 3, 3)} (dbias {(cout,)})")
+    need = _lib.load().wfae_aekl_conv3_wgrad_ws_bytes(kind, n, cin, cout, h, wd)
+    if need == 0:
+        raise _lib.WfaeError(f"aekl_conv3_bwd_weight: unsupported shape N={n} Cin={cin} Cout={cout} {h}x{wd} kind={kind}")
+    ws = workspace(need)
+    _call("wfae_aekl_conv3_bwd_weight", 2 * 9 * n * ho * wo * cin * cout, 4 * (dy.numel() + x.numel() + dw.numel()) + 2 * need,
+          _p(dy), _p(x), _p(scale), _p(shift), _p(dw), _p(dbias), kind, mode, n, cin, cout, h, wd, ws.data_ptr(), ws.numel(),
+          _stream(), label=f"wfae_aekl_conv3_bwd_weight k{kind} {cin}->{cout} {ho}x{wo}", peak=_aekl_peak(mode))
+    return dw
+
+
+def aekl_gn_bwd(du, x, gamma, mean, rstd, skip=None):
+    """GroupNorm backward: du = gradient of gamma xhat + beta -> (dx (+ skip), dgamma, dbeta)"""
+    _chk(du, x, gamma, mean, rstd, skip)
+    n, c = x.shape[:2]
+    hw = x.numel() // max(1, n * c)
+    groups = mean.shape[1]
+    if du.shape != x.shape or tuple(gamma.shape) != (c,) or tuple(mean.shape) != (n, groups) or rstd.shape != mean.shape \
+            or c % groups or (skip is not None and skip.shape != x.shape):
+        raise _lib.WfaeError(f"aekl_gn_bwd: du {tuple(du.shape)}, x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, "
+                             f"mean {tuple(mean.shape)}")
+    dx = torch.empty_like(x)
+    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+    ws = workspace(_lib.load().wfae_aekl_gn_bwd_ws_bytes(n, c, groups))
+    _call("wfae_aekl_gn_bwd", 0, 4 * x.numel() * (6 if skip is not None else 5), _p(du), _p(x), _p(gamma), _p(mean), _p(rstd),
+          _p(skip), _p(dx), _p(dgamma), _p(dbeta), n, c, hw, groups, ws.data_ptr(), ws.numel(), _stream())
+    return dx, dgamma, dbeta
+
+
+def aekl_softmax_bwd(p, dp, scale=1.0):
+    """ds = p (dp - sum_j p_j dp_j) scale for p = softmax(scale * s) over the last dimension"""
+    _chk(p, dp)
+    if p.shape != dp.shape:
+        raise _lib.WfaeError(f"aekl_softmax_bwd: p {tuple(p.shape)} and dp {tuple(dp.shape)} differ")
+    cols = p.shape[-1]
+    ds = torch.empty_like(p)
+    _call("wfae_aekl_softmax_bwd", 0, 12 * p.numel(), _p(p), _p(dp), _p(ds), p.numel() // cols, cols, float(scale), _stream())
+    return ds
+
+
+def aekl_posterior_bwd(moments, dz=None, noise=None, gkl=None):
+    """dmoments (N, 2C, H, W) of sample = mean + std * noise (noise None: the mean) under dz and of the per-sample KL under
+    gkl (N)"""
+    _chk(moments, dz, noise, gkl)
+    n, c2, h, wd = moments.shape
+    shp = (n, c2 // 2, h, wd)
+    if c2 % 2 or any(t is not None and tuple(t.shape) != shp for t in (dz, noise)) or (noise is not None and dz is None) \
+            or (gkl is not None and gkl.numel() != n):
+        raise _lib.WfaeError(f"aekl_posterior_bwd: moments {tuple(moments.shape)} need dz / noise {shp} and gkl ({n},)")
+    dmom = torch.empty_like(moments)
+    _call("wfae_aekl_posterior_bwd", 0, 4 * moments.numel() * 3, _p(dz), _p(noise), _p(moments), _p(gkl), _p(dmom), n, c2 // 2,
+          h * wd, _stream())
+    return dmom
+
+
 # ---- LPIPS perceptual loss (include/wfae.h "LPIPS perceptual loss"; csrc/lpips.hip).  The conv shares the packed weights
 # and the modes of the AutoencoderKL 3x3 kernel: pack with aekl_conv3_pack.
 def _lpips_packed(what, packed, cout, cin, mode):

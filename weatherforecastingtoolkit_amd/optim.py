@@ -202,6 +202,9 @@ class FusedAdamW(torch.optim.Optimizer):
                 if not st:
                     st["m"], st["v"] = torch.zeros_like(p).view(-1), torch.zeros_like(p).view(-1)
                 ops.adamw_(p.data.view(-1), p.grad.contiguous().view(-1), st["m"], st["v"], *args)
+        # the kernel wrote the parameters through raw pointers: tell autograd, as an in-place torch op would.  Caches keyed
+        # on `_version` (the packed 3x3 weights of the AutoencoderKL) see the step; one call, no launch
+        torch.autograd.graph.increment_version([p for g in self.param_groups for p in g["params"]])
         return loss
 
 

@@ -1,12 +1,12 @@
 """Mid-block attention of the frozen AutoencoderKL (reference pipeline/models/autoencoderkl/attention.py
-`AttentionBlock`): GroupNorm, one head over the h*w tokens, projection, residual.  Forward only."""
+`AttentionBlock`): GroupNorm, one head over the h*w tokens, projection, residual; with a graph after `AutoencoderKL.unfreeze()`."""
 from __future__ import annotations
 
 import torch.nn as tnn
 
 from .... import functional as Fn
 from ...._lib import WfaeError
-from .resnet import group_norm_affine
+from .resnet import group_norm_affine, trains
 
 
 class AttentionBlock(tnn.Module):
@@ -31,5 +31,7 @@ class AttentionBlock(tnn.Module):
             raise WfaeError(f"AttentionBlock: tokens S = H*W and channels must be multiples of 32 (got S={s}, "
                             f"C={self.channels})")
         q, k, v, o = self.query, self.key, self.value, self.proj_attn
+        if trains(q.weight):
+            return Fn.aekl_attention_train(x, self.group_norm, q, k, v, o, self.rescale_output_factor)
         return Fn.aekl_attention(x, group_norm_affine(self.group_norm, x), q.weight, q.bias, k.weight, k.bias, v.weight,
                                  v.bias, o.weight, o.bias, self.rescale_output_factor)

@@ -1,16 +1,17 @@
-"""Frozen `AutoencoderKL` latent provider of the v1 experiments on MI355X (reference pipeline/models/autoencoderkl/
-autoencoder_kl.py): the reference's constructor keywords, state_dict keys / order / shapes and seeded initial values;
-`encode(x) -> DiagonalGaussianDistribution`, `decode(z)`, `forward(...)`.  Forward only: the parameters are frozen and an
-input that asks for a gradient is refused (WfaeError) rather than answered without a graph.  A reference checkpoint
-loads with `load_state_dict`."""
+"""`AutoencoderKL` of the v1 experiments on MI355X (reference pipeline/models/autoencoderkl/autoencoder_kl.py): the
+reference's constructor keywords, state_dict keys / order / shapes and seeded initial values;
+`encode(x) -> DiagonalGaussianDistribution`, `decode(z)`, `forward(...)`.  By default it is the frozen latent provider,
+forward only: the parameters are frozen and an input that asks for a gradient is refused (WfaeError) rather than answered
+without a graph.  `unfreeze()` opts into training: the parameters require gradients and the three calls build a graph
+whose backward runs on csrc/aekl_bwd.hip; `freeze()` goes back.  A reference checkpoint loads with `load_state_dict`."""
 from __future__ import annotations
 
 import torch
 import torch.nn as tnn
 
-from .... import ops
 from ...._lib import WfaeError
 from .distributions import DiagonalGaussianDistribution
+from .resnet import conv1x1
 from .vae import Decoder, Encoder
 
 
@@ -35,41 +36,54 @@ class AutoencoderKL(tnn.Module):
         self.quant_conv = tnn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
         self.post_quant_conv = tnn.Conv2d(latent_channels, latent_channels, 1)
         self.use_slicing = False
-        self.eval()
+        self.freeze()
+
+    def freeze(self):
+        """the latent provider (the default): eval mode, no parameter asks for a gradient, no call builds a graph"""
+        self.trainable = False
+        super().train(False)
         for p in self.parameters():
             p.requires_grad_(False)
+        return self
+
+    def unfreeze(self):
+        """opt into training: parameters require gradients, `train(mode)` behaves as for any module, and `encode` /
+        `decode` / `forward` build a graph when autograd is recording"""
+        self.trainable = True
+        for p in self.parameters():
+            p.requires_grad_(True)
+        return self
 
     def train(self, mode=True):
-        return super().train(False)   # frozen: there is no training-mode behaviour
+        return super().train(mode if self.trainable else False)   # frozen: there is no training-mode behaviour
 
-    @staticmethod
-    def _check(what, x, channels):
+    def _check(self, what, x, channels):
         if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != channels:
             raise WfaeError(f"AutoencoderKL.{what}: expected (N, {channels}, H, W), got "
                             f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        if self.trainable:
+            return x.contiguous()
         if torch.is_grad_enabled() and x.requires_grad:
             raise WfaeError(f"AutoencoderKL.{what} is forward only (frozen provider): call it under torch.no_grad() or "
-                            "detach the input")
+                            "detach the input, or opt into training with unfreeze()")
         return x.detach().contiguous()
 
-    @staticmethod
-    def _conv1x1(conv, x):
-        co, ci = conv.out_channels, conv.in_channels
-        return ops.conv1x1_fwd(x, conv.weight.detach().view(co, ci), conv.bias.detach())
+    def _graph(self):
+        return torch.set_grad_enabled(self.trainable and torch.is_grad_enabled())
 
-    @torch.no_grad()
     def _encode(self, x):
         d = self.downscale
         if x.shape[2] % d or x.shape[3] % d:
             raise WfaeError(f"AutoencoderKL.encode: the plane {tuple(x.shape[2:])} is not divisible by {d}")
-        return DiagonalGaussianDistribution(self._conv1x1(self.quant_conv, self.encoder(x)))
+        with self._graph():
+            return DiagonalGaussianDistribution(conv1x1(self.quant_conv, self.encoder(x)))
 
     def encode(self, x):
         return self._encode(self._check("encode", x, self.encoder.conv_in.in_channels))
 
-    @torch.no_grad()
     def _decode(self, z):
-        return self.decoder(self._conv1x1(self.post_quant_conv, z))
+        with self._graph():
+            return self.decoder(conv1x1(self.post_quant_conv, z))
 
     def enable_slicing(self):
         self.use_slicing = True

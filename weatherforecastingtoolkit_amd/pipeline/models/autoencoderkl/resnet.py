@@ -1,5 +1,6 @@
 """Convolutional building blocks of the frozen AutoencoderKL (reference pipeline/models/autoencoderkl/resnet.py:
-`ResnetBlock2D`, `Downsample2D`, `Upsample2D`), forward only, on csrc/aekl.hip.
+`ResnetBlock2D`, `Downsample2D`, `Upsample2D`) on csrc/aekl.hip; after `AutoencoderKL.unfreeze()` with a graph, whose
+backward runs on csrc/aekl_bwd.hip.
 
 The torch classes are parameter containers: created in the reference's order with torch's default initialisation, so
 state_dict keys / order / shapes and the seeded initial values are the reference's.  A block runs as
@@ -9,6 +10,7 @@ the normalised tensors, the padded tensor of `Downsample2D` and the upsampled te
 """
 from __future__ import annotations
 
+import torch
 import torch.nn as tnn
 
 from .... import functional as Fn
@@ -18,33 +20,58 @@ from ...._lib import WfaeError
 GN_EPS = 1e-6
 
 
+def trains(p):
+    """whether a layer with parameter p builds a graph: the parameter was unfrozen and autograd is recording"""
+    return p.requires_grad and torch.is_grad_enabled()
+
+
 class Conv3x3(tnn.Conv2d):
-    """nn.Conv2d(cin, cout, 3) of the provider.  The weights are frozen: they are packed (and split into bf16 planes)
-    once per arithmetic mode and device, again only when the parameter is written (load_state_dict) or moved."""
+    """nn.Conv2d(cin, cout, 3) of the provider.  The weights are packed (and split into bf16 planes) once per arithmetic
+    mode, orientation and device, again only when the parameter is written (load_state_dict, an optimiser step) or moved."""
 
     def __init__(self, cin, cout, stride=1, padding=1):
         super().__init__(cin, cout, kernel_size=3, stride=stride, padding=padding)
         self._packed = {}
 
-    def packed(self, mode):
+    def _pack(self, mode, transposed):
         w = self.weight
         key = (mode, w.device, w.data_ptr(), w._version)
-        hit = self._packed.get(mode)
+        slot = (mode, transposed)
+        hit = self._packed.get(slot)
         if hit is None or hit[0] != key:
-            hit = (key, ops.aekl_conv3_pack(w.detach().contiguous(), mode))
-            self._packed[mode] = hit
+            src = w.detach().flip(2, 3).transpose(0, 1) if transposed else w.detach()
+            hit = (key, ops.aekl_conv3_pack(src.contiguous(), mode))
+            self._packed[slot] = hit
         return hit[1]
 
-    def forward(self, x, gn=None, res=None, kind=0, out_mul=1.0):
+    def packed(self, mode):
+        return self._pack(mode, False)
+
+    def packed_t(self, mode):
+        """the weights rotated 180 degrees with in / out transposed: the operand of the data gradient"""
+        return self._pack(mode, True)
+
+    def forward(self, x, norm=None, res=None, kind=0, out_mul=1.0):
+        """conv3x3(x), or conv3x3(SiLU(norm(x))) with `norm` an nn.GroupNorm; (+ bias + res) * out_mul"""
         if x.dim() != 4 or x.shape[1] != self.in_channels:
             raise WfaeError(f"Conv3x3: expected (N, {self.in_channels}, H, W), got {tuple(x.shape)}")
         mode = ops.aekl_mode()
+        if trains(self.weight):
+            return Fn.aekl_conv3x3_train(x, self, norm, res, kind, out_mul, mode)
+        gn = None if norm is None else group_norm_affine(norm, x)
         return Fn.aekl_conv3x3(x, self.packed(mode), self.out_channels, self.bias, gn, res, kind, out_mul, mode)
 
 
 def group_norm_affine(norm, x):
     """folded (scale, shift) per (sample, channel) of `norm` = nn.GroupNorm on x"""
     return Fn.aekl_group_norm_stats(x, norm.weight, norm.bias, norm.num_groups, norm.eps)[2:]
+
+
+def conv1x1(conv, x):
+    """nn.Conv2d(cin, cout, 1) on the 1x1 kernels"""
+    if trains(conv.weight):
+        return Fn.conv1x1(x, conv.weight, conv.bias)
+    return ops.conv1x1_fwd(x, conv.weight.detach().view(conv.out_channels, conv.in_channels), conv.bias.detach())
 
 
 class Downsample2D(tnn.Module):
@@ -96,9 +123,7 @@ class ResnetBlock2D(tnn.Module):
     def forward(self, x, temb=None):
         if temb is not None:
             raise WfaeError("ResnetBlock2D: the autoencoder has no time embedding")
-        h = self.conv1(x, gn=group_norm_affine(self.norm1, x))
-        gn2 = group_norm_affine(self.norm2, h)
+        h = self.conv1(x, norm=self.norm1)
         if self.conv_shortcut is not None:
-            sc = self.conv_shortcut
-            x = ops.conv1x1_fwd(x, sc.weight.detach().view(self.out_channels, self.in_channels), sc.bias.detach())
-        return self.conv2(h, gn=gn2, res=x, out_mul=1.0 / self.output_scale_factor)
+            x = conv1x1(self.conv_shortcut, x)
+        return self.conv2(h, norm=self.norm2, res=x, out_mul=1.0 / self.output_scale_factor)

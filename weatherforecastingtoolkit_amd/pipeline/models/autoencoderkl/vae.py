@@ -1,10 +1,10 @@
-"""`Encoder` and `Decoder` of the frozen AutoencoderKL (reference pipeline/models/autoencoderkl/vae.py), forward only."""
+"""`Encoder` and `Decoder` of the frozen AutoencoderKL (reference pipeline/models/autoencoderkl/vae.py)."""
 from __future__ import annotations
 
 import torch.nn as tnn
 
 from ...._lib import WfaeError
-from .resnet import GN_EPS, Conv3x3, group_norm_affine
+from .resnet import GN_EPS, Conv3x3
 from .unet_2d_blocks import UNetMidBlock2D, get_down_block, get_up_block
 
 
@@ -41,7 +41,7 @@ class Encoder(tnn.Module):
         for block in self.down_blocks:
             x = block(x)
         x = self.mid_block(x)
-        return self.conv_out(x, gn=group_norm_affine(self.conv_norm_out, x))
+        return self.conv_out(x, norm=self.conv_norm_out)
 
 
 class Decoder(tnn.Module):
@@ -72,4 +72,4 @@ class Decoder(tnn.Module):
         x = self.mid_block(self.conv_in(z))
         for block in self.up_blocks:
             x = block(x)
-        return self.conv_out(x, gn=group_norm_affine(self.conv_norm_out, x))
+        return self.conv_out(x, norm=self.conv_norm_out)
