@@ -1009,6 +1009,44 @@ int wfae_head_dropout_bcast_fwd(const float* v, float* out, int N, int Sq, int H
 int wfae_head_dropout_bcast_bwd(const float* dout, float* dv, int N, int Sq, int H, int D, float p_drop, uint64_t seed,
                                 wfae_stream_t stream);
 
+/* ---- residual autoencoders of ae_gan, evaluation forward (csrc/resae.hip; reference
+ * experiments/v1_experiments/ae_gan/train.py:46-217 `ResidualBlock`, `UpsampleBlock`, `ConvAutoencoder`,
+ * `ConvAutoencoderBIG`).  Added within ABI version 103; nothing changed.
+ * resae_conv:  y = act( conv(x, w) * scale[co] + shift[co] + res ),  NCHW fp32, fp32 accumulation.
+ *   kind 0: 3x3 stride 1 pad 1.  1: 3x3 stride 2 pad 1, Ho = (H - 1) / 2 + 1, input row 2 oy - 1 + ky (NOT
+ *   wfae_aekl_conv3_fwd's kind 1, which pads (0, 1, 0, 1)).  2: 3x3 stride 1 pad 1 over the x2 nearest upsample of x, which
+ *   is never written (Ho = 2 H).  3 / 4: 1x1 with stride 1 / 2 (w is (Cout, Cin, 1, 1)): the centre tap of kind 0 / 1.
+ *   scale, shift (Cout): BatchNorm's running statistics folded per channel, scale = gamma / sqrt(running_var + eps), shift =
+ *   beta - running_mean scale; either may be NULL, a plain bias is shift alone.  res_mode 0: none (res NULL); 1: res (N,
+ *   Cout, Ho, Wo); 2: res (N, Cout, Ho / 2, Wo / 2) read as res[n, co, oy >> 1, ox >> 1] (Ho, Wo even).  act 0: none, 1:
+ *   the exact (erf) GELU.
+ *   route 0, "tile": an implicit GEMM on the matrix cores for any shape, 64 output channels x 8 x 16 pixels of one sample per
+ *   workgroup; mode 1 / 3 / 4 = bf16 operands / three bf16 planes (fp32 accuracy) / fp32 MFMA, as wfae_aekl_conv3_fwd.
+ *   route 1, "small": output planes of at most 16 pixels (else WFAE_ERR_UNSUPPORTED).  The GEMM's columns are the output
+ *   pixels of all samples; a workgroup owns 64 output channels x 64 columns x a share of K and reads its fp32 weights once
+ *   (mode is ignored: fp32 MFMA); K is split over workgroups where the output channels do not fill the chip and finished
+ *   from ws (wfae_resae_workspace_bytes, 0 when no split is made) in ascending order.  A tap is DEAD when no output position
+ *   of the layer reads a real input pixel through it (wfae_resae_live_taps: bit ky * 3 + kx set = live, the layout of
+ *   wfae_c3s2_live_taps; kinds 3 / 4: the centre bit): dead taps are neither fetched nor multiplied, live taps that are
+ *   padding for one column contribute literal zeros.
+ *   Fixed summation order on both routes, no atomics: two launches give the same bits.
+ * resae_pack: w (Cout, Cin, 3, 3) (kinds 0..2) or (Cout, Cin, 1, 1) (kinds 3, 4), the RAW weights, -> the operand of
+ *   resae_conv for (route, kind, mode), wfae_resae_pack_bytes bytes (0 for arguments that are refused), 16-byte aligned.
+ *   route 0: [plane][32-channel chunk][tap][co padded to 64][32 ci], wfae_aekl_conv3_pack's layout; route 1: fp32 in MFMA
+ *   fragment order, [tap][16 co][16 ci] blocks.
+ * Errors, all before any launch: null x / packed / y / w WFAE_ERR_NULL_POINTER; an unknown route, kind, mode (route 0),
+ *   res_mode or act, res_mode that does not go with res, a size < 1, a plane above 8192, an odd output plane with res_mode 2,
+ *   a sample of 2^31 elements, a misaligned packed WFAE_ERR_BAD_SHAPE; channel counts above 4096, and on route 1 a larger
+ *   output plane or N Ho Wo >= 2^21, WFAE_ERR_UNSUPPORTED; a short or misaligned workspace WFAE_ERR_WORKSPACE. */
+int wfae_resae_live_taps(int kind, int H, int W);
+size_t wfae_resae_pack_bytes(int route, int kind, int mode, int Cout, int Cin);
+int wfae_resae_pack(const float* w, void* packed, int route, int kind, int mode, int Cout, int Cin, wfae_stream_t stream);
+size_t wfae_resae_workspace_bytes(int kind, int N, int Cin, int Cout, int H, int W);
+int wfae_resae_conv(const float* x, const void* packed, const float* scale /* may be NULL */, const float* shift /* may be NULL */,
+                    const float* res /* NULL iff res_mode = 0 */, float* y, int route, int kind, int mode, int res_mode, int act,
+                    int N, int Cin, int Cout, int H, int W, void* ws /* may be NULL when no bytes are needed */, size_t ws_bytes,
+                    wfae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,11 @@ class Autoencoder(tnn.Module):
     dict, or a Lightning checkpoint that holds it under the `autoencoder.` / `model.` prefix, other modules' keys next to
     it being ignored), else a seeded initialisation
     (`cfg.seed`, default 0).  encode returns the posterior's mode; frames go through in chunks of `cfg.chunk_frames`.
-    The conv and AutoencoderKL kinds also `decode` — act(dec(z)) for each frame — so that validation / test can score
+    kind "ae_gan.convautoencoder": the residual `ConvAutoencoderBIG` of ae_gan in evaluation mode (`cfg.latent_dim`, default
+    2048; `cfg.checkpoint` / `cfg.seed` as for autoencoder_kl): encode (B, T, 1, 128, 128) -> (B, T, latent_dim, 1, 1), decode
+    back to frames, the raw `final_conv` output as in the reference; frames go through in chunks of `cfg.chunk_frames`
+    (default 64: the 1x1 .. 4x4 layers are a weight stream, so a chunk should be large; the 64 x 64 activations bound it).
+    The conv, AutoencoderKL and ae_gan kinds also `decode` — act(dec(z)) for each frame — so that validation / test can score
     forecasts in frame space like the reference (pretrained_ae_dlinear_*/train.py:196-200)."""
 
     AEKL_KEYS = ("in_channels", "out_channels", "down_block_types", "up_block_types", "block_out_channels",
@@ -35,6 +39,11 @@ class Autoencoder(tnn.Module):
         if kind == "autoencoder_kl":
             self.autoencoder = self._build_autoencoder_kl(cfg or {})
             self.chunk_frames = int((cfg or {}).get("chunk_frames") or 8)
+            if self.chunk_frames < 1:
+                raise ValueError(f"autoencoder.chunk_frames={self.chunk_frames}")
+        elif kind == "ae_gan.convautoencoder":
+            self.autoencoder = self._build_ae_gan(cfg or {})
+            self.chunk_frames = int((cfg or {}).get("chunk_frames") or 64)
             if self.chunk_frames < 1:
                 raise ValueError(f"autoencoder.chunk_frames={self.chunk_frames}")
         elif kind == "ae_vit.tokens":
@@ -69,6 +78,16 @@ class Autoencoder(tnn.Module):
             torch.manual_seed(int(cfg.get("seed") or 0))
             return AutoencoderKL(**kw)
 
+    @staticmethod
+    def _build_ae_gan(cfg):
+        from ._ae_gan import ConvAutoencoderBIG, load_checkpoint
+        latent_dim = int(cfg.get("latent_dim") or 2048)
+        if cfg.get("checkpoint"):
+            return load_checkpoint(ConvAutoencoderBIG(latent_dim=latent_dim), cfg["checkpoint"])
+        with torch.random.fork_rng(devices=[]):     # the seeded initialisation does not move the caller's generator
+            torch.manual_seed(int(cfg.get("seed") or 0))
+            return ConvAutoencoderBIG(latent_dim=latent_dim)
+
     def _chunks(self, frames):
         n = self.chunk_frames if self.chunk_frames > 0 else frames.shape[0]
         return [frames[i:i + n].contiguous() for i in range(0, frames.shape[0], n)]
@@ -79,6 +98,8 @@ class Autoencoder(tnn.Module):
         frames = x.reshape(b * t, c, h, w)
         if self.kind == "autoencoder_kl":
             z = torch.cat([self.autoencoder.encode(f).mode() for f in self._chunks(frames)])
+        elif self.kind == "ae_gan.convautoencoder":
+            z = torch.cat([self.autoencoder.encode(f) for f in self._chunks(frames)])[:, :, None, None]
         elif self.kind == "ae_vit.tokens":
             tok = self.autoencoder.encode_tokens(frames)                      # (B*T, 64, 512)
             s = self.autoencoder.seq
@@ -88,7 +109,7 @@ class Autoencoder(tnn.Module):
         return z.view(b, t, *z.shape[1:])
 
     def can_decode(self):
-        return self.kind in ("ae_64x8x8_lin.enc", "autoencoder_kl")
+        return self.kind in ("ae_64x8x8_lin.enc", "autoencoder_kl", "ae_gan.convautoencoder")
 
     @torch.no_grad()
     def decode(self, z):
@@ -99,6 +120,9 @@ class Autoencoder(tnn.Module):
         ae = self.autoencoder
         if self.kind == "autoencoder_kl":
             x = torch.cat([ae.decode(f) for f in self._chunks(z.reshape(b * t, *z.shape[2:]))])
+            return x.view(b, t, *x.shape[1:])
+        if self.kind == "ae_gan.convautoencoder":
+            x = torch.cat([ae.decode(f) for f in self._chunks(z.reshape(b * t, -1))])
             return x.view(b, t, *x.shape[1:])
         x = ae.act(ae.dec(z.reshape(b * t, *z.shape[2:]).contiguous()))
         return x.view(b, t, *x.shape[1:])

@@ -2499,3 +2499,115 @@ def head_dropout_bcast_bwd(dout, n, sq, h, p_drop=0.0, seed=0):
     _call("wfae_head_dropout_bcast_bwd", 0, 4 * (dv.numel() + dout.numel()), _p(dout), _p(dv), n, sq, h, e // h, p_drop, seed,
           _stream())
     return dv
+
+
+# ---- residual autoencoder: the ae_gan models in evaluation mode (include/wfae.h "residual autoencoders of ae_gan";
+# csrc/resae.hip).  One unit, y = act(conv(x, w) * scale + shift + res), on two routes; `resae_route` alone decides.
+RESAE_KINDS = {"conv": 0, "down": 1, "up": 2, "short": 3, "short_down": 4}
+RESAE_ROUTES = {"tile": 0, "small": 1}
+RESAE_SMALL_PLANE = 16     # output pixels up to which the small-plane route serves a layer
+
+
+def resae_out_plane(kind, h, wd):
+    """output plane of `kind` on an h x wd input"""
+    if kind == 2:
+        return 2 * h, 2 * wd
+    if kind in (1, 4):
+        return (h - 1) // 2 + 1, (wd - 1) // 2 + 1
+    return h, wd
+
+
+def resae_live_taps(kind, h, wd):
+    """-> the 3 x 3 nested list of booleans: tap (ky, kx) is live iff some output position reads a real input pixel through
+    it; the library's rule (wfae_resae_live_taps, bit ky * 3 + kx), which is the one the kernels use"""
+    mask = _lib.load().wfae_resae_live_taps(int(kind), int(h), int(wd))
+    if mask < 0:
+        raise _lib.WfaeError(f"resae_live_taps: kind {kind!r} on a {h}x{wd} plane")
+    return [[bool(mask >> (ky * 3 + kx) & 1) for kx in range(3)] for ky in range(3)]
+
+
+def resae_route(kind, N, Cin, Cout, H, W):
+    """-> "small" | "tile": the small-plane route wherever it serves the layer (an output plane of at most 16 pixels).
+    Measured faster there on every such layer of ConvAutoencoderBIG (256 to 2048 channels) at B = 8 and B = 32
+    (profiles/resae_bench.jsonl); for other channel counts and batch sizes, ConvAutoencoder's
+    1024-channel layers among them, the rule is extrapolated from those rows, not measured."""
+    ho, wo = resae_out_plane(kind, H, W)
+    return "small" if ho * wo <= RESAE_SMALL_PLANE else "tile"
+
+
+class ResaePacked:
+    """packed weights of one layer for one (route, kind, mode)"""
+    __slots__ = ("data", "route", "kind", "mode", "cout", "cin")
+
+    def __init__(self, data, route, kind, mode, cout, cin):
+        self.data, self.route, self.kind, self.mode, self.cout, self.cin = data, route, kind, mode, cout, cin
+
+
+def _resae_kind(what, kind):
+    kind = RESAE_KINDS.get(kind, kind)
+    if kind not in RESAE_KINDS.values():
+        raise _lib.WfaeError(f"{what}: kind {kind!r}, expected one of {sorted(RESAE_KINDS)} (0..4)")
+    return kind
+
+
+def resae_pack(w, kind, route, mode=None):
+    """raw weights (Cout, Cin, 3, 3), or (Cout, Cin, 1, 1) for the shortcut kinds, -> ResaePacked for `route`"""
+    _chk(w)
+    kind = _resae_kind("resae_pack", kind)
+    if route not in RESAE_ROUTES:
+        raise _lib.WfaeError(f"resae_pack: route {route!r}, expected 'small' or 'tile'")
+    mode = aekl_mode() if mode is None else mode
+    k = 1 if kind >= 3 else 3
+    if w.dim() != 4 or tuple(w.shape[2:]) != (k, k):
+        raise _lib.WfaeError(f"resae_pack: weight shape {tuple(w.shape)}, expected (Cout, Cin, {k}, {k}) for kind {kind}")
+    cout, cin = w.shape[:2]
+    nbytes = _lib.load().wfae_resae_pack_bytes(RESAE_ROUTES[route], kind, mode, cout, cin)
+    if nbytes == 0:
+        raise _lib.WfaeError(f"resae_pack: unsupported Cout={cout} Cin={cin} mode={mode}")
+    data = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    _call("wfae_resae_pack", 0, 4 * w.numel() + nbytes, _p(w), data.data_ptr(), RESAE_ROUTES[route], kind, mode, cout, cin,
+          _stream())
+    return ResaePacked(data, route, kind, mode, cout, cin)
+
+
+def resae_fold(gamma, beta, running_mean, running_var, eps=1e-5):
+    """BatchNorm's running statistics folded per channel, in fp64 on the host, stored as fp32 on the parameters' device:
+    -> (scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale)"""
+    g, b, m, v = (t.detach().to("cpu", torch.float64) for t in (gamma, beta, running_mean, running_var))
+    scale = g / torch.sqrt(v + eps)
+    shift = b - m * scale
+    return scale.to(gamma.device, torch.float32), shift.to(gamma.device, torch.float32)
+
+
+def resae_conv(x, packed, scale=None, shift=None, res=None, res_up=False, act=False, route=None):
+    """y = act(conv(x) * scale + shift + res): the one launch of the residual autoencoders.  packed: resae_pack's, for the
+    route `resae_route` gives this shape (or the `route=` override of the tests and the bench); res (N, Cout, Ho, Wo), or
+    with res_up (N, Cout, Ho / 2, Wo / 2) read through a x2 nearest upsample; act: exact GELU"""
+    _chk(x, scale, shift, res)
+    if x.dim() != 4 or x.shape[1] != packed.cin:
+        raise _lib.WfaeError(f"resae_conv: expected (N, {packed.cin}, H, W), got {tuple(x.shape)}")
+    n, cin, h, wd = x.shape
+    kind, cout = packed.kind, packed.cout
+    want = resae_route(kind, n, cin, cout, h, wd) if route is None else route
+    if want != packed.route or packed.data.device != x.device:
+        raise _lib.WfaeError(f"resae_conv: weights packed for route {packed.route!r} on {packed.data.device}, the launch is "
+                             f"route {want!r} on {x.device}")
+    ho, wo = resae_out_plane(kind, h, wd)
+    for name, v in (("scale", scale), ("shift", shift)):
+        if v is not None and tuple(v.shape) != (cout,):
+            raise _lib.WfaeError(f"resae_conv: {name} {tuple(v.shape)}, expected {(cout,)}")
+    rshape = (n, cout, ho // 2, wo // 2) if res_up else (n, cout, ho, wo)
+    if res is not None and (tuple(res.shape) != rshape or (res_up and (ho % 2 or wo % 2))):
+        raise _lib.WfaeError(f"resae_conv: residual {tuple(res.shape)}, expected {rshape}")
+    y = torch.empty((n, cout, ho, wo), dtype=torch.float32, device=x.device)
+    ws_bytes = _lib.load().wfae_resae_workspace_bytes(kind, n, cin, cout, h, wd) if want == "small" else 0
+    ws = workspace(ws_bytes) if ws_bytes else None
+    taps = sum(map(sum, resae_live_taps(kind, h, wd)))
+    wbytes = 4 * cout * cin * taps if want == "small" else packed.data.numel()
+    _call("wfae_resae_conv", 2 * taps * n * ho * wo * cin * cout,
+          wbytes + 4 * (x.numel() + y.numel() + (res.numel() if res is not None else 0)), _p(x), packed.data.data_ptr(),
+          _p(scale), _p(shift), _p(res), _p(y), RESAE_ROUTES[want], kind, packed.mode, (2 if res_up else 1) if res is not None else 0,
+          int(bool(act)), n, cin, cout, h, wd, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _stream(),
+          label=f"wfae_resae_conv {want} k{kind} {cin}->{cout} {ho}x{wo}",
+          peak=PEAK_FP32_MFMA if want == "small" else _aekl_peak(packed.mode))
+    return y
