@@ -1047,6 +1047,58 @@ int wfae_resae_conv(const float* x, const void* packed, const float* scale /* ma
                     int N, int Cin, int Cout, int H, int W, void* ws /* may be NULL when no bytes are needed */, size_t ws_bytes,
                     wfae_stream_t stream);
 
+/* ---- residual autoencoders of ae_gan, backward (csrc/resae_bwd.hip).  Added within ABI version 103; nothing changed.
+ * kind, N, Cin, Cout, H, W are the FORWARD layer's (wfae_resae_conv): x (N, Cin, H, W), dy (N, Cout, Ho, Wo), the raw
+ * weight (Cout, Cin, k, k).  NCHW fp32, the fp32 matrix instruction, fixed summation order, no atomics: two launches
+ * give the same bits.  Both gradients are GEMMs over groups of 64 COLUMNS, one per pixel:
+ *   route 1, "small": the columns are the pixels of all samples in (n, y, x) order; Ho Wo <= 16 and N H W < 2^21 (else
+ *   WFAE_ERR_UNSUPPORTED).  route 0, "tile": a group is an 8 x 8 tile of one sample; any shape.
+ *   Dead taps (wfae_resae_live_taps) are never read: their weight gradient is exactly 0.0 and their weights, whatever they
+ *   hold, do not reach dx.
+ * resae_bwd_pack: the raw weight -> packed_t, the data gradient's operand on both routes (in and out channels transposed,
+ *   fp32 in MFMA fragment order, [tap][16 ci][16 co] blocks; the tap keeps its forward index and the kernel runs the
+ *   geometry backwards, which is the 180-degree rotation), wfae_resae_bwd_pack_bytes bytes, 16-byte aligned.
+ * resae_bwd_data: dx (N, Cin, H, W) = dgrad(dy) + add; add (dx's shape) may be NULL.  Written, not accumulated.  Kind 1:
+ *   dy row (iy + 1 - ky) / 2 where that is exact and in range; kind 4: the 1x1 product at even positions, exact zeros
+ *   elsewhere; kind 2: the gradient on the x2 grid with each 2 x 2 block summed, the upsampled tensor is never written.
+ *   Where K = Cout is split over workgroups (small route), and for kind 2 on the small route, the partial sums go to ws
+ *   (wfae_resae_bwd_data_workspace_bytes) and a finishing launch adds them in ascending order.
+ * resae_bwd_weight: dw in the raw shape (Cout, Cin, k, k), written, not accumulated, each (co, ci)'s taps as one run;
+ *   dbias (Cout) = the sum of dy over (n, oy, ox), may be NULL.  K is the columns of all samples together; where they are
+ *   split over workgroups the partial dw go to ws (wfae_resae_bwd_weight_workspace_bytes; one slab per SPLIT, never per
+ *   sample) and are added in ascending order.
+ * resae_join_fwd: the end of a train-mode block,  y = gelu(c2 s2[c] + h2[c] + r'),  r' = r ss[c] + hs[c] (the shortcut
+ *   convolution under its own BatchNorm) or r itself where ss and hs are NULL (identity shortcut); c2, y (N, C, H, W);
+ *   res_mode 1: r (N, C, H, W); 2: r (N, C, H / 2, W / 2) read as r[n, c, oy >> 1, ox >> 1] (H, W even).
+ * resae_join_bwd: one pass that rebuilds the pre-activation and writes dpre = dy gelu'(pre); at res_mode 2 also dres (r's
+ *   shape), each 2 x 2 block of dpre summed in row-major order (dres NULL exactly at res_mode 1, where it is dpre).
+ * resae_bn_running: the running-statistics update of a train-mode BatchNorm whose input is read through the x2 upsample
+ *   (the shortcut of an UpsampleBlock, which runs at the source resolution): from the saved batch mean and invstd of the
+ *   source tensor (wfae_bn_stats_train with NULL running statistics), with the unbiased factor count / (count - 1) for
+ *   count = 4 N H W, the number of values nn.BatchNorm2d sees on the upsampled tensor.
+ * Errors, all before any launch: null required pointers WFAE_ERR_NULL_POINTER; an unknown route, kind or res_mode, a size
+ *   < 1, a plane above 8192, an odd plane with res_mode 2, one of ss / hs without the other, dres that does not go with
+ *   res_mode, a sample of 2^31 elements, a misaligned packed_t WFAE_ERR_BAD_SHAPE; channel counts above 4096, and on route
+ *   1 a larger plane, WFAE_ERR_UNSUPPORTED; a short or misaligned workspace WFAE_ERR_WORKSPACE. */
+size_t wfae_resae_bwd_pack_bytes(int kind, int Cout, int Cin);
+int wfae_resae_bwd_pack(const float* w, void* packed_t, int kind, int Cout, int Cin, wfae_stream_t stream);
+size_t wfae_resae_bwd_data_workspace_bytes(int route, int kind, int N, int Cin, int Cout, int H, int W);
+int wfae_resae_bwd_data(const float* dy, const void* packed_t, const float* add /* may be NULL */, float* dx, int route, int kind,
+                        int N, int Cin, int Cout, int H, int W, void* ws /* may be NULL when no bytes are needed */,
+                        size_t ws_bytes, wfae_stream_t stream);
+size_t wfae_resae_bwd_weight_workspace_bytes(int route, int kind, int N, int Cin, int Cout, int H, int W);
+int wfae_resae_bwd_weight(const float* dy, const float* x, float* dw, float* dbias /* may be NULL */, int route, int kind, int N,
+                          int Cin, int Cout, int H, int W, void* ws /* may be NULL when no bytes are needed */, size_t ws_bytes,
+                          wfae_stream_t stream);
+int wfae_resae_join_fwd(const float* c2, const float* s2, const float* h2, const float* r, const float* ss /* may be NULL */,
+                        const float* hs /* NULL iff ss is */, float* y, int res_mode, int N, int C, int H, int W,
+                        wfae_stream_t stream);
+int wfae_resae_join_bwd(const float* dy, const float* c2, const float* s2, const float* h2, const float* r,
+                        const float* ss /* may be NULL */, const float* hs /* NULL iff ss is */, float* dpre,
+                        float* dres /* NULL iff res_mode = 1 */, int res_mode, int N, int C, int H, int W, wfae_stream_t stream);
+int wfae_resae_bn_running(const float* save_mean, const float* save_invstd, float* running_mean, float* running_var, int C,
+                          float eps, float momentum, int64_t count, wfae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
-"""Residual autoencoders of the reference's experiments/v1_experiments/ae_gan/train.py in EVALUATION mode, without
-Lightning / W&B: `ResidualBlock` (:46-77), `UpsampleBlock` (:79-86), `ConvAutoencoder` (:88-154), `ConvAutoencoderBIG`
-(:156-217) and the test / validation side of `Model` (:403-510), on csrc/resae.hip.
+"""Residual autoencoders of the reference's experiments/v1_experiments/ae_gan/train.py without Lightning / W&B:
+`ResidualBlock` (:46-77), `UpsampleBlock` (:79-86), `ConvAutoencoder` (:88-154), `ConvAutoencoderBIG` (:156-217) and
+`Model` (:403-510) below `lpips.disc_start`, on csrc/resae.hip (forward) and csrc/resae_bwd.hip (backward).
 
 The torch classes are parameter containers: created in the reference's order with torch's default initialisation, so
 state_dict keys / order / shapes and the seeded initial values are the reference's.  In evaluation mode every layer of a
@@ -15,9 +15,15 @@ with BatchNorm's running statistics folded into scale / shift.  A block is three
 Packed weights and folded statistics are cached on the layer and redone when a parameter or buffer is written
 (load_state_dict) or moved.
 
-Forward only.  Not built, and left to the follow-up that trains these models: train-mode BatchNorm (batch statistics,
-running-stat updates), every gradient, the two-optimiser GAN step.  `ConvAutoencoder2` and `AttentionChargedAutoencoder`
-(stride 4 / scale factor 4) are not built either.
+Training is an opt-in: blocks and models are created frozen (evaluation mode, no gradients, a training-mode call is
+refused) and `unfreeze()` makes them trainable, as `AutoencoderKL.unfreeze()` does.  An unfrozen block in training mode
+is one autograd Function (functional.ResaeBlockFn): raw convolutions, batch statistics with the running-statistics
+update, the join kernel, and in the backward the data / weight gradients of csrc/resae_bwd.hip; in evaluation mode it
+runs the folded path above.  `Model(cfg, trainable=True)` is the reference's training step below `disc_start`: L1 on the
+autoencoder with one optimiser (the run its shipped config does: disc_start 1.0, disc_weight 0, perceptual_weight 0).
+
+Not built: the discriminator / adaptive-weight branch of the loss and its second optimiser, LPIPS in this experiment,
+`ConvAutoencoder2` and `AttentionChargedAutoencoder` (stride 4 / scale factor 4).
 """
 from __future__ import annotations
 
@@ -28,9 +34,11 @@ from ... import functional as Fn
 from ... import ops
 from ..._lib import WfaeError
 from ...pipeline import helpers
+from ._runner import Step
 
-FOLLOW_UP = ("the ae_gan residual autoencoders are built forward-only (evaluation mode, running statistics); train-mode "
-             "BatchNorm, the backward kernels and the GAN training step are the follow-up to this feature")
+FOLLOW_UP = ("this block or model is frozen and runs forward-only (evaluation mode, running statistics): unfreeze() it, or "
+             "build Model(cfg, trainable=True), to train it.  The discriminator branch of the GAN step remains the follow-up "
+             "to this feature")
 SKIPPED_PREFIXES = ("loss.discriminator.", "loss.perceptual_loss.")
 
 
@@ -41,6 +49,7 @@ class Conv(tnn.Conv2d):
     def __init__(self, cin, cout, kernel_size, stride=1, bias=False):
         super().__init__(cin, cout, kernel_size=kernel_size, stride=stride, padding=kernel_size // 2, bias=bias)
         self._packed = {}
+        self._packed_t = None
 
     def packed(self, kind, route, mode):
         w = self.weight
@@ -51,6 +60,15 @@ class Conv(tnn.Conv2d):
             hit = (key, ops.resae_pack(w.detach(), kind, route, mode))
             self._packed[slot] = hit
         return hit[1]
+
+    def packed_t(self, kind):
+        """the data gradient's operand (ops.resae_bwd_pack), packed once per parameter version"""
+        w = self.weight
+        kind = ops.RESAE_KINDS[kind]
+        key = (kind, w.device, w.data_ptr(), w._version)
+        if self._packed_t is None or self._packed_t[0] != key:
+            self._packed_t = (key, ops.resae_bwd_pack(w.detach(), kind))
+        return self._packed_t[1]
 
     def forward(self, x, kind, scale=None, shift=None, res=None, res_up=False, act=False, route=None):
         if x.dim() != 4 or x.shape[1] != self.in_channels:
@@ -68,6 +86,20 @@ class FoldedBatchNorm(tnn.BatchNorm2d):
     def __init__(self, c):
         super().__init__(c)
         self._folded = None
+        self._nbt_pending = 0      # training steps not yet added to num_batches_tracked (nn.BatchNorm2d of this package)
+
+    def flush(self):
+        if self._nbt_pending:
+            self.num_batches_tracked += self._nbt_pending
+            self._nbt_pending = 0
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        self.flush()
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+
+    def _load_from_state_dict(self, *a, **kw):
+        self._nbt_pending = 0
+        super()._load_from_state_dict(*a, **kw)
 
     def folded(self):
         ts = (self.weight, self.bias, self.running_mean, self.running_var)
@@ -77,7 +109,9 @@ class FoldedBatchNorm(tnn.BatchNorm2d):
         return self._folded[1]
 
     def forward(self, x):
-        raise WfaeError("FoldedBatchNorm is applied in the epilogue of the convolution in front of it; " + FOLLOW_UP)
+        raise WfaeError("FoldedBatchNorm is not a layer of its own: it is applied in the epilogue of the convolution in front of "
+                        "it (evaluation) or inside the block's autograd Function (training); a stand-alone BatchNorm of these "
+                        "models would be a follow-up")
 
 
 def _freeze(m):
@@ -86,7 +120,29 @@ def _freeze(m):
     return m.eval()
 
 
-class ResidualBlock(tnn.Module):
+class _Trainable:
+    """`unfreeze()` / `freeze()` of the blocks and models, as AutoencoderKL has them; `_trainable` is what a training-mode
+    call asks for"""
+
+    _trainable = False
+
+    def _set_trainable(self, flag):
+        for m in self.modules():
+            if isinstance(m, _Trainable):
+                m._trainable = flag
+        for p in self.parameters():
+            p.requires_grad_(flag)
+        return self
+
+    def unfreeze(self):
+        """parameters require gradients, `train(mode)` behaves as for any module; stays in the mode it is in"""
+        return self._set_trainable(True)
+
+    def freeze(self):
+        return self._set_trainable(False).eval()
+
+
+class ResidualBlock(_Trainable, tnn.Module):
     """reference :46-77"""
 
     def __init__(self, in_ch, out_ch, stride=1):
@@ -106,13 +162,20 @@ class ResidualBlock(tnn.Module):
         self.act2 = tnn.GELU()
         _freeze(self)
 
-    @torch.no_grad()
     def forward(self, x, up=False, route=None):
         """up: the block reads x through a x2 nearest upsample (UpsampleBlock); route: force "small" / "tile" (tests)"""
-        if self.training:
+        if self.training and not self._trainable:
             raise WfaeError("ResidualBlock.forward in training mode: " + FOLLOW_UP)
         if up and self.stride != 1:
             raise WfaeError("ResidualBlock: the upsampled form has stride 1")
+        if self.training:
+            if x.dim() != 4 or x.shape[1] != self.conv1.in_channels:
+                raise WfaeError(f"ResidualBlock: expected (N, {self.conv1.in_channels}, H, W), got {tuple(x.shape)}")
+            return Fn.resae_block_train(self, x, up, route)
+        with torch.no_grad():
+            return self._eval(x, up, route)
+
+    def _eval(self, x, up, route):
         short = x
         if len(self.shortcut):
             conv, bn = self.shortcut
@@ -121,7 +184,7 @@ class ResidualBlock(tnn.Module):
         return self.conv2(h, "conv", *self.bn2.folded(), res=short, res_up=up, act=True, route=route)
 
 
-class UpsampleBlock(tnn.Module):
+class UpsampleBlock(_Trainable, tnn.Module):
     """reference :79-86; the upsampled tensor is never written"""
 
     def __init__(self, in_ch, out_ch, scale_factor=2):
@@ -133,12 +196,12 @@ class UpsampleBlock(tnn.Module):
         self.eval()
 
     def forward(self, x, route=None):
-        if self.training:
+        if self.training and not self._trainable:
             raise WfaeError("UpsampleBlock.forward in training mode: " + FOLLOW_UP)
         return self.resblock(x, up=True, route=route)
 
 
-class _Autoencoder(tnn.Module):
+class _Autoencoder(_Trainable, tnn.Module):
     """what the two models share: encode / decode / forward over `enc1..enc7`, `fc_enc`, `fc_dec`, (`dec_init_conv`,)
     `dec1..dec7`, `final_conv`; `stages` collects every block's output (tests)"""
 
@@ -147,25 +210,33 @@ class _Autoencoder(tnn.Module):
     def _check(self, what, x, shape):
         if x.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, x.shape)):
             raise WfaeError(f"{type(self).__name__}.{what}: expected {shape} (None = any), got {tuple(x.shape)}")
-        if self.training:
+        if self.training and not self._trainable:
             raise WfaeError(f"{type(self).__name__}.{what} in training mode: " + FOLLOW_UP)
 
-    @staticmethod
-    def _linear(lin, x):
+    def _grad_mode(self):
+        """autograd sees the forward only in training mode (of an unfrozen model); evaluation runs the folded kernels"""
+        return torch.enable_grad() if self.training and torch.is_grad_enabled() else torch.no_grad()
+
+    def _linear(self, lin, x):
+        if self.training:
+            return Fn.LinearFn.apply(x, lin.weight, lin.bias)
         return ops.linear_fwd(x.contiguous(), lin.weight.detach(), lin.bias.detach())
 
-    @torch.no_grad()
     def encode(self, x, stages=None):
         self._check("encode", x, (None, self.enc1.conv1.in_channels, 128, 128))
-        for i in range(1, 8):
-            x = getattr(self, f"enc{i}")(x)
-            if stages is not None:
-                stages[f"enc{i}"] = x
-        return self._linear(self.fc_enc, x.view(x.shape[0], -1))
+        with self._grad_mode():
+            for i in range(1, 8):
+                x = getattr(self, f"enc{i}")(x)
+                if stages is not None:
+                    stages[f"enc{i}"] = x
+            return self._linear(self.fc_enc, x.reshape(x.shape[0], -1))
 
-    @torch.no_grad()
     def decode(self, z, stages=None):
         self._check("decode", z, (None, self.fc_enc.out_features))
+        with self._grad_mode():
+            return self._decode(z, stages)
+
+    def _decode(self, z, stages):
         x = self._linear(self.fc_dec, z).view(z.shape[0], self.top, 1, 1)
         if hasattr(self, "dec_init_conv"):
             x = self.dec_init_conv(x)
@@ -175,6 +246,8 @@ class _Autoencoder(tnn.Module):
             x = getattr(self, f"dec{i}")(x)
             if stages is not None:
                 stages[f"dec{i}"] = x
+        if self.training:
+            return Fn.resae_conv_train(self.final_conv, x, "conv")
         return self.final_conv(x, "conv", shift=self.final_conv.bias.detach())
 
     def forward(self, x):
@@ -266,16 +339,20 @@ def load_checkpoint(autoencoder, path):
     return autoencoder
 
 
-class Model(tnn.Module):
-    """reference Model (:403-510), its validation / test side: `autoencoder`, `forward`, `get_last_layer`,
-    `validation_step`, `test_step` with the loss's `global_step < disc_start` branch (:359-373), the only one the shipped
-    config (`disc_start: 1.0` of the total steps) reaches"""
+class Model(Step, tnn.Module):
+    """reference Model (:403-510) with the loss's `global_step < disc_start` branch (:359-373), the only one the shipped
+    config (`disc_start: 1.0` of the total steps) reaches: `autoencoder`, `forward`, `get_last_layer`, `validation_step`,
+    `test_step`, and with `trainable=True` the generator half of `training_step` (:439-457) on `_runner.Step`"""
 
-    def __init__(self, cfg, autoencoder=None):
+    trained = "autoencoder"
+    exact_complements = True
+
+    def __init__(self, cfg, autoencoder=None, trainable=False):
         super().__init__()
         if autoencoder is not None:
             raise WfaeError("ae_gan evaluates its own autoencoder: it takes no latent provider")
         self.cfg = cfg
+        self.trainable = bool(trainable)
         name = cfg.model.name
         if name == "convautoencoder":
             self.autoencoder = ConvAutoencoderBIG(latent_dim=cfg.ConvAutoencoder.latent_dim)       # reference :409-410
@@ -288,15 +365,22 @@ class Model(tnn.Module):
             load_checkpoint(self.autoencoder, cfg.model.checkpoint)
         lp = cfg.lpips
         if lp.perceptual_weight > 0:
-            raise WfaeError(f"lpips.perceptual_weight={lp.perceptual_weight}: the perceptual term belongs to the training "
-                            "step; " + FOLLOW_UP)
+            raise WfaeError(f"lpips.perceptual_weight={lp.perceptual_weight}: the perceptual (LPIPS) term of this experiment "
+                            "is not built; the shipped config has 0")
         self.disc_start, self.recon_weight = lp.disc_start, lp.recon_weight
         self.global_step = 0
+        self.logs = {}
+        if self.trainable:
+            if cfg.trainer.accumulate_grad_batches != 1:
+                raise WfaeError("Model: trainer.accumulate_grad_batches must be 1 (the shipped value)")
+            self.total_steps = cfg.trainer.total_train_steps
+            self.autoencoder.unfreeze()
 
     def train(self, mode=True):
-        """the autoencoder stays in evaluation mode"""
+        """a model that is not trainable keeps its autoencoder in evaluation mode"""
         super().train(mode)
-        self.autoencoder.eval()
+        if not self.trainable:
+            self.autoencoder.eval()
         return self
 
     def forward(self, x):
@@ -314,18 +398,37 @@ class Model(tnn.Module):
             raise WfaeError(f"Model: expected frames (B, T, H, W), got {tuple(batch.shape)}")
         return batch.reshape(-1, 1, batch.shape[2], batch.shape[3]).contiguous()
 
+    def _refuse_disc(self, what):
+        if self.global_step >= self.disc_start:
+            raise WfaeError(f"Model.{what} at global_step {self.global_step} >= lpips.disc_start {self.disc_start}: "
+                            "the discriminator branch of the loss and its optimiser are not built")
+
     def training_step(self, batch, batch_idx=0):
-        raise WfaeError("Model.training_step: " + FOLLOW_UP)
+        """reference :439-457 below disc_start: rec_loss = recon_weight * L1, backward, clip at optim.gradient_clip_val,
+        AdamW, schedule -> (loss, gradient norm before clipping); the logs of the loss (:366-371) are left in `self.logs`"""
+        if not self.trainable:
+            raise WfaeError("Model.training_step: " + FOLLOW_UP)
+        self._refuse_disc("training_step")
+        if not hasattr(self, "opt"):
+            raise WfaeError("Model.training_step: call configure_optimizers() first")
+        self.autoencoder.train()        # the shared driver leaves `autoencoder` attributes in evaluation mode
+        inp = self.frames(batch)
+        rec = Fn.l1_loss(self(inp), inp, float(self.recon_weight))
+        loss, gn = self.optimizer_step(rec)
+        self.logs = {"train/total_loss": loss, "train/rec_loss": loss, "train/g_loss": 0.0, "train/d_weight": 0.0,
+                     "train/g_grad_norm": gn}
+        self.global_step += 1
+        return loss, gn
 
     def configure_optimizers(self):
-        raise WfaeError("Model.configure_optimizers: " + FOLLOW_UP)
+        if not self.trainable:
+            raise WfaeError("Model.configure_optimizers: " + FOLLOW_UP)
+        return Step.configure_optimizers(self)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0, split="val"):
         """reference :482-510 below disc_start -> (rec_loss, logs)"""
-        if self.global_step >= self.disc_start:
-            raise WfaeError(f"Model.{split} step at global_step {self.global_step} >= lpips.disc_start {self.disc_start}: "
-                            "the discriminator branch of the loss is not built; " + FOLLOW_UP)
+        self._refuse_disc(f"{split} step")
         inp = self.frames(batch)
         pred = self(inp)
         rec = Fn.l1_loss(pred, inp, float(self.recon_weight))
@@ -335,3 +438,8 @@ class Model(tnn.Module):
 
     def test_step(self, batch, batch_idx=0):
         return self.validation_step(batch, batch_idx, split="test")
+
+
+def model_state(model):
+    """what `last.ckpt` holds, in Lightning's spelling: `autoencoder.*` (`autoencoder_state` / `load_checkpoint` read it)"""
+    return {"autoencoder." + k: v for k, v in model.autoencoder.state_dict().items()}

@@ -1766,3 +1766,110 @@ class SplitInProjFn(Function):
         dxq = ops.linear_bwd_data(dq, w[:e]) if ctx.needs_input_grad[0] else None
         dxkv = ops.linear_bwd_data(dkv, w[e:]) if ctx.needs_input_grad[1] else None
         return dxq, dxkv, dw, db, None
+
+
+# ---- training the ae_gan residual autoencoders (csrc/resae_bwd.hip): the autograd Functions behind `unfreeze()` of
+# experiments/v1_experiments/_ae_gan.py.  One Function per block; the upsampled tensor is never written and never saved.
+def _resae_bn(x, bn, replicas=1):
+    """train-mode statistics of `bn` on x, the running-statistics update included; the kernels write the buffers through
+    raw pointers, so their version counters are bumped here for the caches keyed on them (FoldedBatchNorm.folded)"""
+    st = ops.resae_bn_stats_train(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, replicas)
+    bn._nbt_pending += 1
+    torch.autograd.graph.increment_version([bn.running_mean, bn.running_var])
+    return st
+
+
+def _st4(st):
+    return st.mean, st.invstd, st.scale, st.shift
+
+
+class ResaeBlockFn(Function):
+    """ResidualBlock in training mode, also read through the x2 upsample (UpsampleBlock):
+        c1 = conv1(x)           stride 1, stride 2, or over the upsample
+        h  = gelu(bn1(c1))
+        c2 = conv2(h)
+        cs = shortcut conv(x)   at the block INPUT's resolution (or none: the identity shortcut)
+        y  = gelu(bn2(c2) + bn_s(cs) or x)                       ops.resae_join_fwd
+    with batch statistics.  `blk` is the module: it owns the packed weights and the BatchNorm buffers."""
+
+    @staticmethod
+    def forward(ctx, x, w1, g1, b1, w2, g2, b2, ws, gs, bs, blk, up, route):
+        x = _c(x)
+        k1 = "up" if up else "down" if blk.stride == 2 else "conv"
+        c1 = blk.conv1(x, k1, route=route)
+        st1 = _resae_bn(c1, blk.bn1)
+        h = ops.bn_act_fwd(c1, st1, 1)
+        c2 = blk.conv2(h, "conv", route=route)
+        st2 = _resae_bn(c2, blk.bn2)
+        cs, sts = None, None
+        if ws is not None:
+            cs = blk.shortcut[0](x, "short_down" if blk.stride == 2 else "short", route=route)
+            sts = _resae_bn(cs, blk.shortcut[1], 4 if up else 1)
+        y = ops.resae_join_fwd(c2, st2.scale, st2.shift, x if cs is None else cs, None if sts is None else sts.scale,
+                               None if sts is None else sts.shift, res_up=up)
+        ctx.save_for_backward(x, w1, g1, w2, g2, ws, gs, c1, h, c2, cs, *_st4(st1), *_st4(st2), *(_st4(sts) if sts else ()))
+        ctx.blk, ctx.up, ctx.route, ctx.k1 = blk, up, route, k1
+        ctx.betas = (b1, b2, bs)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, g1, w2, g2, ws, gs, c1, h, c2, cs, *s = ctx.saved_tensors
+        blk, up, route = ctx.blk, ctx.up, ctx.route
+        b1, b2, bs = ctx.betas
+        st1, st2 = _mk_stats(*s[0:4]), _mk_stats(*s[4:8])
+        sts = _mk_stats(*s[8:12]) if cs is not None else None
+        dpre, dres = ops.resae_join_bwd(_c(dy), c2, st2.scale, st2.shift, x if cs is None else cs,
+                                        None if sts is None else sts.scale, None if sts is None else sts.shift, res_up=up)
+        dg2, db2 = grad_buffer(g2), grad_buffer(b2)
+        dc2 = ops.bn_act_bwd(dpre, c2, g2, st2, dg2, db2, None, 0, True)
+        dw2 = grad_buffer(w2)
+        ops.resae_bwd_weight(dc2, h, dw2, "conv", route=route)
+        dh = ops.resae_bwd_data(dc2, blk.conv2.packed_t("conv"), h.shape, route=route)
+        dg1, db1 = grad_buffer(g1), grad_buffer(b1)
+        dc1 = ops.bn_act_bwd(dh, c1, g1, st1, dg1, db1, None, 1, True)
+        dw1 = grad_buffer(w1)
+        ops.resae_bwd_weight(dc1, x, dw1, ctx.k1, route=route)
+        need_dx = ctx.needs_input_grad[0]
+        dws = dgs = dbs = None
+        side = dres                       # the identity shortcut: the join's gradient at r is x's
+        if cs is not None:
+            ks = "short_down" if blk.stride == 2 else "short"
+            dgs, dbs = grad_buffer(gs), grad_buffer(bs)
+            dcs = ops.bn_act_bwd(dres, cs, gs, sts, dgs, dbs, None, 0, True)
+            dws = grad_buffer(ws)
+            ops.resae_bwd_weight(dcs, x, dws, ks, route=route)
+            side = ops.resae_bwd_data(dcs, blk.shortcut[0].packed_t(ks), x.shape, route=route) if need_dx else None
+        dx = ops.resae_bwd_data(dc1, blk.conv1.packed_t(ctx.k1), x.shape, add=side, route=route) if need_dx else None
+        return dx, dw1, dg1, db1, dw2, dg2, db2, dws, dgs, dbs, None, None, None
+
+
+def resae_block_train(blk, x, up=False, route=None):
+    sc = blk.shortcut
+    ws, gs, bs = (sc[0].weight, sc[1].weight, sc[1].bias) if len(sc) else (None, None, None)
+    return ResaeBlockFn.apply(x, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias, blk.conv2.weight, blk.bn2.weight, blk.bn2.bias,
+                              ws, gs, bs, blk, bool(up), route)
+
+
+class ResaeConvFn(Function):
+    """a plain convolution of the residual autoencoders with a bias (`final_conv`): ops.resae_conv and its two gradients"""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, conv, kind, route):
+        x = _c(x)
+        ctx.save_for_backward(x, w)
+        ctx.conv, ctx.bias, ctx.kind, ctx.route = conv, bias, kind, route
+        return conv(x, kind, shift=bias, route=route)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = _c(dy)
+        dw, dbias = grad_buffer(w), None if ctx.bias is None else grad_buffer(ctx.bias)
+        ops.resae_bwd_weight(dy, x, dw, ctx.kind, dbias=dbias, route=ctx.route)
+        dx = ops.resae_bwd_data(dy, ctx.conv.packed_t(ctx.kind), x.shape, route=ctx.route) if ctx.needs_input_grad[0] else None
+        return dx, dw, dbias, None, None, None
+
+
+def resae_conv_train(conv, x, kind="conv", route=None):
+    return ResaeConvFn.apply(x, conv.weight, conv.bias, conv, kind, route)

@@ -2611,3 +2611,157 @@ def resae_conv(x, packed, scale=None, shift=None, res=None, res_up=False, act=Fa
           label=f"wfae_resae_conv {want} k{kind} {cin}->{cout} {ho}x{wo}",
           peak=PEAK_FP32_MFMA if want == "small" else _aekl_peak(packed.mode))
     return y
+
+
+# ---- residual autoencoder, backward (include/wfae.h "residual autoencoders of ae_gan, backward"; csrc/resae_bwd.hip): the
+# data and the weight gradient of the five kinds on two routes, `resae_bwd_route` alone decides; the join of a train-mode
+# block forward and backward.
+def resae_bwd_route(what, kind, N, Cin, Cout, H, W):
+    """-> "small" | "tile" for what = "data" | "weight" of the layer (kind, N, Cin, Cout, H, W: the forward's).  The
+    small-plane route wherever it serves the layer: an output plane of at most 16 pixels, the forward's rule (`resae_route`).
+    Both gradients follow it; DESIGN.md "Training the residual autoencoders" has the rows it rests on."""
+    if what not in ("data", "weight"):
+        raise _lib.WfaeError(f"resae_bwd_route: what {what!r}, expected 'data' or 'weight'")
+    ho, wo = resae_out_plane(kind, H, W)
+    return "small" if ho * wo <= RESAE_SMALL_PLANE else "tile"
+
+
+class ResaePackedT:
+    """the data gradient's operand of one layer: the weight with in and out channels transposed (both routes)"""
+    __slots__ = ("data", "kind", "cout", "cin")
+
+    def __init__(self, data, kind, cout, cin):
+        self.data, self.kind, self.cout, self.cin = data, kind, cout, cin
+
+
+def resae_bwd_pack(w, kind):
+    """raw weights (Cout, Cin, k, k) -> ResaePackedT"""
+    _chk(w)
+    kind = _resae_kind("resae_bwd_pack", kind)
+    k = 1 if kind >= 3 else 3
+    if w.dim() != 4 or tuple(w.shape[2:]) != (k, k):
+        raise _lib.WfaeError(f"resae_bwd_pack: weight shape {tuple(w.shape)}, expected (Cout, Cin, {k}, {k}) for kind {kind}")
+    cout, cin = w.shape[:2]
+    nbytes = _lib.load().wfae_resae_bwd_pack_bytes(kind, cout, cin)
+    if nbytes == 0:
+        raise _lib.WfaeError(f"resae_bwd_pack: unsupported Cout={cout} Cin={cin}")
+    data = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    _call("wfae_resae_bwd_pack", 0, 4 * w.numel() + nbytes, _p(w), data.data_ptr(), kind, cout, cin, _stream())
+    return ResaePackedT(data, kind, cout, cin)
+
+
+def _resae_bwd_shapes(what, kind, dy, cin, cout, x_shape):
+    """checks dy (N, Cout, Ho, Wo) against the forward input shape (N, Cin, H, W) -> (n, h, wd, ho, wo)"""
+    if len(x_shape) != 4 or x_shape[1] != cin:
+        raise _lib.WfaeError(f"{what}: input shape {tuple(x_shape)}, expected (N, {cin}, H, W)")
+    n, _, h, wd = x_shape
+    ho, wo = resae_out_plane(kind, h, wd)
+    if tuple(dy.shape) != (n, cout, ho, wo):
+        raise _lib.WfaeError(f"{what}: dy {tuple(dy.shape)}, expected {(n, cout, ho, wo)} for kind {kind} on {tuple(x_shape)}")
+    return n, h, wd, ho, wo
+
+
+def _resae_bwd_route_arg(what, which, route, kind, n, cin, cout, h, wd):
+    route = resae_bwd_route(which, kind, n, cin, cout, h, wd) if route is None else route
+    if route not in RESAE_ROUTES:
+        raise _lib.WfaeError(f"{what}: route {route!r}, expected 'small' or 'tile'")
+    return route
+
+
+def resae_bwd_data(dy, packed_t, x_shape, add=None, route=None):
+    """dx = dgrad(dy) + add for the layer whose forward input had `x_shape`; packed_t: resae_bwd_pack's; add: dx's shape"""
+    _chk(dy, add)
+    kind, cin, cout = packed_t.kind, packed_t.cin, packed_t.cout
+    n, h, wd, ho, wo = _resae_bwd_shapes("resae_bwd_data", kind, dy, cin, cout, tuple(x_shape))
+    if add is not None and tuple(add.shape) != (n, cin, h, wd):
+        raise _lib.WfaeError(f"resae_bwd_data: add {tuple(add.shape)}, expected {(n, cin, h, wd)}")
+    if packed_t.data.device != dy.device:
+        raise _lib.WfaeError(f"resae_bwd_data: weights packed on {packed_t.data.device}, dy on {dy.device}")
+    route = _resae_bwd_route_arg("resae_bwd_data", "data", route, kind, n, cin, cout, h, wd)
+    dx = torch.empty((n, cin, h, wd), dtype=torch.float32, device=dy.device)
+    ws_bytes = _lib.load().wfae_resae_bwd_data_workspace_bytes(RESAE_ROUTES[route], kind, n, cin, cout, h, wd)
+    ws = workspace(ws_bytes) if ws_bytes else None
+    taps = sum(map(sum, resae_live_taps(kind, h, wd)))
+    _call("wfae_resae_bwd_data", 2 * taps * n * ho * wo * cin * cout,
+          4 * (cout * cin * taps + dy.numel() + dx.numel() * (2 if add is not None else 1)), _p(dy), packed_t.data.data_ptr(),
+          _p(add), _p(dx), RESAE_ROUTES[route], kind, n, cin, cout, h, wd, None if ws is None else ws.data_ptr(),
+          0 if ws is None else ws.numel(), _stream(), label=f"wfae_resae_bwd_data {route} k{kind} {cin}<-{cout} {ho}x{wo}",
+          peak=PEAK_FP32_MFMA)
+    return dx
+
+
+def resae_bwd_weight(dy, x, dw, kind, dbias=None, route=None):
+    """dw (Cout, Cin, k, k) = wgrad(dy, x), written (exact zeros in dead taps); dbias (Cout) = the sum of dy, optional"""
+    _chk(dy, x, dw, dbias)
+    kind = _resae_kind("resae_bwd_weight", kind)
+    k = 1 if kind >= 3 else 3
+    if dw.dim() != 4 or tuple(dw.shape[2:]) != (k, k):
+        raise _lib.WfaeError(f"resae_bwd_weight: dw shape {tuple(dw.shape)}, expected (Cout, Cin, {k}, {k}) for kind {kind}")
+    cout, cin = dw.shape[:2]
+    n, h, wd, ho, wo = _resae_bwd_shapes("resae_bwd_weight", kind, dy, cin, cout, tuple(x.shape))
+    if dbias is not None and tuple(dbias.shape) != (cout,):
+        raise _lib.WfaeError(f"resae_bwd_weight: dbias {tuple(dbias.shape)}, expected {(cout,)}")
+    route = _resae_bwd_route_arg("resae_bwd_weight", "weight", route, kind, n, cin, cout, h, wd)
+    ws_bytes = _lib.load().wfae_resae_bwd_weight_workspace_bytes(RESAE_ROUTES[route], kind, n, cin, cout, h, wd)
+    ws = workspace(ws_bytes) if ws_bytes else None
+    taps = sum(map(sum, resae_live_taps(kind, h, wd)))
+    _call("wfae_resae_bwd_weight", 2 * taps * n * ho * wo * cin * cout, 4 * (dw.numel() + dy.numel() + x.numel()), _p(dy), _p(x),
+          _p(dw), _p(dbias), RESAE_ROUTES[route], kind, n, cin, cout, h, wd, None if ws is None else ws.data_ptr(),
+          0 if ws is None else ws.numel(), _stream(), label=f"wfae_resae_bwd_weight {route} k{kind} {cin}->{cout} {ho}x{wo}",
+          peak=PEAK_FP32_MFMA)
+    return dw
+
+
+def _resae_join_args(what, c2, s2, h2, r, ss, hs, res_up):
+    _chk(c2, s2, h2, r, ss, hs)
+    if c2.dim() != 4:
+        raise _lib.WfaeError(f"{what}: expected c2 (N, C, H, W), got {tuple(c2.shape)}")
+    n, c, h, wd = c2.shape
+    rshape = (n, c, h // 2, wd // 2) if res_up else (n, c, h, wd)
+    if tuple(r.shape) != rshape or (res_up and (h % 2 or wd % 2)):
+        raise _lib.WfaeError(f"{what}: residual {tuple(r.shape)}, expected {rshape}")
+    if (ss is None) != (hs is None):
+        raise _lib.WfaeError(f"{what}: ss and hs go together")
+    for name, v in (("s2", s2), ("h2", h2), ("ss", ss), ("hs", hs)):
+        if v is not None and tuple(v.shape) != (c,):
+            raise _lib.WfaeError(f"{what}: {name} {tuple(v.shape)}, expected {(c,)}")
+    return n, c, h, wd
+
+
+def resae_join_fwd(c2, s2, h2, r, ss=None, hs=None, res_up=False):
+    """y = gelu(c2 s2[c] + h2[c] + r'), r' = r ss[c] + hs[c] or r itself; res_up: r at half resolution"""
+    n, c, h, wd = _resae_join_args("resae_join_fwd", c2, s2, h2, r, ss, hs, res_up)
+    y = torch.empty_like(c2)
+    _call("wfae_resae_join_fwd", 0, 4 * (2 * c2.numel() + r.numel()), _p(c2), _p(s2), _p(h2), _p(r), _p(ss), _p(hs), _p(y),
+          2 if res_up else 1, n, c, h, wd, _stream())
+    return y
+
+
+def resae_join_bwd(dy, c2, s2, h2, r, ss=None, hs=None, res_up=False):
+    """-> (dpre = dy gelu'(pre), dres): dres is dpre itself at the same resolution, its 2 x 2 block sums with res_up"""
+    n, c, h, wd = _resae_join_args("resae_join_bwd", c2, s2, h2, r, ss, hs, res_up)
+    _chk(dy)
+    if dy.shape != c2.shape:
+        raise _lib.WfaeError(f"resae_join_bwd: dy {tuple(dy.shape)}, expected {tuple(c2.shape)}")
+    dpre = torch.empty_like(c2)
+    dres = torch.empty_like(r) if res_up else None
+    _call("wfae_resae_join_bwd", 0, 4 * (3 * c2.numel() + 2 * r.numel()), _p(dy), _p(c2), _p(s2), _p(h2), _p(r), _p(ss), _p(hs),
+          _p(dpre), _p(dres), 2 if res_up else 1, n, c, h, wd, _stream())
+    return dpre, (dres if res_up else dpre)
+
+
+def resae_bn_stats_train(x, gamma, beta, running_mean, running_var, eps=1e-5, momentum=0.1, replicas=1):
+    """bn_stats_train for a block of the residual autoencoders.  replicas = 4: x is what the reference's BatchNorm sees
+    through the x2 upsample (the shortcut of an UpsampleBlock, kept at the source resolution): the batch statistics are
+    x's, the unbiased factor of the running variance counts every value four times.  A single value per channel raises
+    ValueError, as nn.BatchNorm2d does in training mode."""
+    nb, c, h, wd = x.shape
+    if nb * h * wd * replicas <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+    if replicas == 1:
+        return bn_stats_train(x, gamma, beta, running_mean, running_var, eps, momentum)
+    _chk(running_mean, running_var)
+    st = bn_stats_train(x, gamma, beta, None, None, eps, momentum)
+    _call("wfae_resae_bn_running", 0, 16 * c, _p(st.mean), _p(st.invstd), _p(running_mean), _p(running_var), c, eps, momentum,
+          nb * h * wd * replicas, _stream())
+    return st
