@@ -210,6 +210,23 @@ int wfae_get_c1wd(void);
 int wfae_c1wd_supported(int C, int mid, int HW);
 int wfae_c1wd_bwd(const float* dy, const float* t2, const float* bn_scale, const float* bn_shift, const float* w3, float* dw3,
                   float* da3, int NB, int C, int mid, int HW, int accumulate, void* ws, size_t ws_bytes, wfae_stream_t stream);
+/* The two passes of a Bottleneck's backward that read the block input x (NB,C,HW) in front of the first BatchNorm's sums at
+ * C = 128 / 256, mid = C / 4, in ONE pass over x (csrc/c1ws.hip): dw1 (mid,C) (+)= dt1 . gelu(x * bn_scale[c] + bn_shift[c])^T —
+ * the result of wfae_c1w_bwd_weight on the same arguments, bit for bit — and the partial rows of sum dU / sum dU xhat that
+ * wfae_c1r_bnred(da = NULL) leaves (dU = (w1^T dt1) gelu'(x bn_scale + bn_shift); the same fp32 sums of four pixels, added in
+ * fp64 in another order): `part` = [rows][C] ++ [rows][C] doubles, one row per workgroup, *part_rows = rows =
+ * wfae_c1ws_stat_rows(C, mid, NB, HW, ws_bytes) (0: not served); finish with wfae_bn_act_bwd_from_rows.  fp32 tensors at fp32
+ * precision with the split GEMMs on, HW % 64 == 0, x and dt1 16-byte aligned; ws as wfae_c1w_bwd_weight.
+ * wfae_c1ws_supported: 1 when the shape is served and the switch is on (wfae_set_c1ws, on by default; environment WFAE_C1WS=0
+ * turns it off at load) — otherwise wfae_c1ws_bwd returns WFAE_ERR_UNSUPPORTED and the caller runs the two launches.
+ * Process-wide; read at launch. */
+int wfae_set_c1ws(int on);
+int wfae_get_c1ws(void);
+int wfae_c1ws_supported(int C, int mid, int HW);
+int wfae_c1ws_stat_rows(int C, int mid, int NB, int HW, size_t ws_bytes);
+int wfae_c1ws_bwd(const float* x, const float* dt1, const float* bn_scale, const float* bn_shift, const float* save_mean,
+                  const float* save_invstd, const float* w1, float* dw1, double* part, int64_t part_capacity, int* part_rows, int NB,
+                  int C, int mid, int HW, int accumulate, void* ws, size_t ws_bytes, wfae_stream_t stream);
 /* ---- nn.Linear (to_latent / from_latent, ae_64x8x8_lin.py:74-75,92,98) ---
  * y[b,o] = sum_i x[b,i] w[o,i] + bias[o] */
 int wfae_linear_fwd(const float* x, const float* w, const float* bias, float* y, int B, int In,

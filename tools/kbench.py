@@ -200,6 +200,32 @@ def main():
                         report(f"c1wd C {c} @{h}x{w_} {tag} pass{rep}", ms, fl, by)
                         acc(f"c1wd_{c}_{h * w_}_{tag.split()[0]}_pass{rep}", ms)
                 del dy, t2, w3, dw
+    if "c1ws" in only:
+        # csrc/c1ws.hip (dW1 and the sums of the first BatchNorm's backward from one pass over x) against the pair c1r_bnred
+        # (sums alone) + c1w, at the shapes of --only c1wd; two passes, pair and fused interleaved: the spread of the pair between
+        # its passes is the noise the gain is read against
+        for rep in range(-1, 2):     # pass -1 warms the clocks up and is not reported
+            for c, h, w_ in [(128, S, S), (256, S // 2, S // 2), (128, 96, 96), (128, 64, 64), (128, 32, 32), (128, 16, 32), (256, 96, 96),
+                             (256, 64, 64), (256, 32, 32), (256, 16, 32)]:
+                mid = c // 4
+                n = B * h * w_
+                x, dt1 = rnd(B, c, h, w_) * 4, rnd(B, mid, h, w_)
+                w1, dw = rnd(mid, c, 1, 1) * 0.1, torch.empty(mid, c, 1, 1, device=dev)
+                st = ops.bn_stats_train(x, torch.rand(c, device=dev) + 0.5, torch.rand(c, device=dev) - 0.5, torch.zeros(c, device=dev),
+                                        torch.ones(c, device=dev))
+                assert ops.conv1x1_ws_supported(c, mid, h * w_)
+
+                def pair():
+                    ops.conv1x1_bwd_weight_bnact(dt1, x, st, dw)
+                    return ops.c1r_bnred(w1, dt1, x, st, store=False)
+
+                fl, by_pair, by_fused = 4 * n * c * mid, 4 * n * (2 * c + 2 * mid), 4 * n * (c + mid)
+                for tag, fn, by in [("pair c1w + c1r_bnred", pair, by_pair), ("fused c1ws", lambda: ops.conv1x1_bwd_ws(dt1, x, st, w1, dw), by_fused)]:
+                    ms = timeit(fn, R)
+                    if rep >= 0:
+                        report(f"c1ws C {c} @{h}x{w_} {tag} pass{rep}", ms, fl, by)
+                        acc(f"c1ws_{c}_{h * w_}_{tag.split()[0]}_pass{rep}", ms)
+                del x, dt1, w1, dw
     if "bnseq" in only:
         # first BatchNorm of a Bottleneck, backward: data gradient of the C -> C/4 convolution + BatchNorm/GELU backward (+ residual
         # gradient), with the reduce pass separate or in the c1r epilogue (ops.set_c1r_bnred)

@@ -586,9 +586,15 @@ def _c1(w, plane, transposed, x, st=None, res=None, stats=False, fam=None):
 _b16 = _c1      # (the name tests/ reach it by: it served the bf16-stored tensors only)
 
 
-def _dgrad_bn(dt, w, Wt, x, gamma, st, dgamma, dbeta, res, training):
+def _dgrad_bn(dt, w, Wt, x, gamma, st, dgamma, dbeta, res, training, rows=None):
     """dx of  conv1x1(gelu(bn(x)), w)  given dt = dL/d(conv output): the data gradient dA = W^T dT followed by the
-    BatchNorm + GELU backward at x (+ res, the residual-branch gradient); Wt: the bf16 plane of w^T for csrc/c1b.hip, or empty"""
+    BatchNorm + GELU backward at x (+ res, the residual-branch gradient); Wt: the bf16 plane of w^T for csrc/c1b.hip, or empty;
+    rows: the StatRows of sum dU / sum dU xhat when ops.conv1x1_bwd_ws has taken them already (the 'bndx' route)"""
+    if rows is not None:
+        # the sums came with the weight gradient: straight to the finish and the second pass.  from_rows writes the coefficients
+        # at the head of the workspace whose slabs the fused launch's slab_reduce has read — same stream, in this order
+        ops.bn_act_bwd_from_rows(rows, x.shape[1], dgamma, dbeta)
+        return ops.c1r_bndx(w, dt, x, gamma, st, res, training)
     how = ops.conv1x1_dgrad_bn_route(w.shape[1], dt.shape[1], dt.shape[2] * dt.shape[3], _storage(dt))
     if how is not None:
         # the C <= 256 widening data gradients on csrc/c1r.hip: sum dU / sum dU xhat of the BatchNorm in front ride in the epilogue
@@ -689,12 +695,18 @@ class BottleneckFn(Function):
         dt1 = ops.bn_act_bwd(da2, t1, g2, st2, dg2, db2, None, 1, tr)
         del da2
         dw1 = grad_buffer(w1)
+        rows1 = None
         if a1.numel() == 0:     # a1 was never materialised: the weight gradient rebuilds it from x in its loader
-            _wgrad(lambda: ops.conv1x1_bwd_weight_bnact(dt1, x, st1, dw1), dt1, x, st1.scale, st1.shift)
+            if ops.conv1x1_ws_route(x.shape[1], mid, x.shape[2] * x.shape[3], _storage(x)) == "c1ws":
+                # dW1 and the sums of the first BatchNorm's backward in one pass over x, on the main stream: it writes a gradient
+                # buffer and its rows are needed there at once
+                rows1 = _on_main(lambda: ops.conv1x1_bwd_ws(dt1, x, st1, w1, dw1))
+            if rows1 is None:
+                _wgrad(lambda: ops.conv1x1_bwd_weight_bnact(dt1, x, st1, dw1), dt1, x, st1.scale, st1.shift)
         else:
             _wgrad(lambda: ops.conv1x1_bwd_weight(dt1, a1, dw1), dt1, a1)
         dg1, db1 = grad_buffer(g1), grad_buffer(ctx.betas[0])
-        dx = _dgrad_bn(dt1, w1, W1t, x, g1, st1, dg1, db1, dy, tr)
+        dx = _dgrad_bn(dt1, w1, W1t, x, g1, st1, dg1, db1, dy, tr, rows1)
         return dx, dg1, db1, dw1, dg2, db2, dwg, dg3, db3, dw3, None, None
 
 

@@ -281,6 +281,12 @@ def set_c1wd(on):
     _lib.call("wfae_set_c1wd", int(bool(on)))
 
 
+def set_c1ws(on):
+    """A/B switch: the first 1x1 weight gradient and the sums of the first BatchNorm's backward of a C <= 256 Bottleneck in one
+    pass over x (csrc/c1ws.hip) or as the pair c1r_bnred(store=False) + c1w"""
+    _lib.call("wfae_set_c1ws", int(bool(on)))
+
+
 def set_c1rb(on):
     """A/B switch: the bf16 1x1 forward / data gradient on csrc/c1rb.hip (register-direct) or on csrc/c1b.hip (LDS-tiled)"""
     global _C1RB
@@ -309,6 +315,10 @@ def c1n_enabled():
 
 def c1wd_enabled():
     return bool(_lib.load().wfae_get_c1wd())
+
+
+def c1ws_enabled():
+    return bool(_lib.load().wfae_get_c1ws())
 
 
 def _precision():
@@ -589,6 +599,51 @@ def conv1x1_bwd_wd(dy, t2, st, w3, dw3, accumulate=False):
           _p(dw3), _p(da), nb, c, mid, hw, int(accumulate), ws.data_ptr(), ws.numel(), _stream(), peak=PEAK_BF16_MFMA / 6,
           label="wfae_c1wd_bwd")
     return da
+
+
+def conv1x1_ws_supported(c, mid, hw, storage="f32"):
+    """csrc/c1ws.hip serves the shape AND the two launches it replaces are today's pair (c1w weight gradient with the BatchNorm +
+    GELU prologue, whose bits it keeps, and the sums-alone c1r_bnred in front of c1r_bndx, whose fp32 quads it adds up in fp64):
+    C in (128, 256), mid = C / 4, hw % 64 == 0, fp32 tensors at fp32 precision with the split GEMMs on, set_c1ws / set_c1w /
+    set_c1r / set_c1r_bnred / set_c1r_bndx on"""
+    return (storage == "f32" and _SPLIT_GEMM and _precision() == 0 and bool(_lib.load().wfae_c1ws_supported(int(c), int(mid), int(hw)))
+            and conv1x1_route("wgrad", mid, c, hw, "f32", True) == "c1w" and conv1x1_dgrad_bn_route(c, mid, hw, storage) == "bndx")
+
+
+def conv1x1_ws_route(c, mid, hw, storage="f32"):
+    """How a Bottleneck's backward computes dW1 and the sums of the first BatchNorm's backward from x and dT1 when a1 was not
+    materialised: 'c1ws' — one launch that reads x once (conv1x1_bwd_ws) — or 'pair' — conv1x1_bwd_weight_bnact + the sums-alone
+    c1r_bnred.  Below C1WD_MIN_HW pixels both forms are launch-bound (nothing below was measured; the launch traces recorded
+    at 128 and 192 pixels, tests/golden/g19_c1_launches.json, hold the pair)."""
+    return "c1ws" if hw >= C1WD_MIN_HW and conv1x1_ws_supported(c, mid, hw, storage) else "pair"
+
+
+def conv1x1_bwd_ws(dt1, x, st, w1, dw1, accumulate=False):
+    """dw1 (+)= dt1 . gelu(bn(x))^T as conv1x1_bwd_weight_bnact(dt1, x, st, dw1), bit for bit, and the partial rows of
+    c1r_bnred(w1, dt1, x, st, store=False) (the same fp32 sums of four pixels, added in fp64 in another order), in one pass over x
+    (csrc/c1ws.hip) -> StatRows, to be finished by bn_act_bwd_from_rows; None: not served (nothing launched, the caller runs
+    the pair) — st None (the activated tensor was materialised), bf16-stored tensors, other shapes, set_c1ws(False)"""
+    if st is None or dt1.dtype != torch.float32 or x.dtype != torch.float32:
+        return None
+    nb, c, h, wd = x.shape
+    mid, hw = dt1.shape[1], h * wd
+    if not conv1x1_ws_supported(c, mid, hw):
+        return None
+    _chk(dt1, x, w1, dw1)
+    if tuple(dt1.shape) != (nb, mid, h, wd) or w1.numel() != c * mid or dw1.numel() != c * mid:
+        raise _lib.WfaeError("conv1x1_bwd_ws: x (N, C, H, W), dt1 (N, C/4, H, W), w1 and dw1 (C/4, C)")
+    if (dt1.data_ptr() | x.data_ptr()) & 15:
+        return None
+    n = nb * hw
+    ws = workspace()
+    cap = 2 * int(_lib.load().wfae_c1ws_stat_rows(c, mid, nb, hw, ws.numel())) * c
+    if cap <= 0:
+        return None
+    part, rows, out = _rows_out(cap, x.device)
+    _call("wfae_c1ws_bwd", 4 * n * c * mid, 4 * n * (c + mid) + 8 * c * mid, _p(x), _p(dt1), _p(st.scale), _p(st.shift), _p(st.mean),
+          _p(st.invstd), _p(w1), _p(dw1), *out, nb, c, mid, hw, int(accumulate), ws.data_ptr(), ws.numel(), _stream(),
+          peak=PEAK_BF16_MFMA / 6, label="wfae_c1ws_bwd")
+    return StatRows(part[:2 * rows.value * c], rows.value)
 
 
 def c1r_bnred(w, dt, x, st, store=True):
