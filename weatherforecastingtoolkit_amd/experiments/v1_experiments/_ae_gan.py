@@ -403,6 +403,14 @@ class Model(Step, tnn.Module):
             raise WfaeError(f"Model.{what} at global_step {self.global_step} >= lpips.disc_start {self.disc_start}: "
                             "the discriminator branch of the loss and its optimiser are not built")
 
+    def validation_refused(self):
+        """why a validation / test pass cannot run at this `global_step` (the driver prints it and goes on), or None:
+        from `disc_start` on the steps are refused, and a fit ends exactly there"""
+        if self.global_step >= self.disc_start:
+            return (f"global_step {self.global_step} >= lpips.disc_start {self.disc_start}: the discriminator branch of "
+                    "the loss is not built")
+        return None
+
     def training_step(self, batch, batch_idx=0):
         """reference :439-457 below disc_start: rec_loss = recon_weight * L1, backward, clip at optim.gradient_clip_val,
         AdamW, schedule -> (loss, gradient norm before clipping); the logs of the loss (:366-371) are left in `self.logs`"""

@@ -131,6 +131,9 @@ class Model(Step, tnn.Module):
         self._dp_d = parallel.DataParallelTrainer(self.loss.discriminator, self.d_opt)
         return self.opt, self.d_opt
 
+    def optimizers(self):
+        return [(self.opt, self.sch), (self.d_opt, self.d_sch)]
+
     @staticmethod
     def frames(batch):
         """the loader's batch (a tensor or its dict; (B, T, H, W) or (B, 1, H, W) frames) -> (B * T, 1, H, W)"""

@@ -247,6 +247,9 @@ class Model(Step, tnn.Module):
         self._dp_d = parallel.DataParallelTrainer(self.loss.discriminator, self.d_opt)
         return self.opt, self.d_opt
 
+    def optimizers(self):
+        return [(self.opt, self.sch), (self.d_opt, self.d_sch)]
+
     def latents(self, batch):
         """-> (frames (B, T, 1, H, W) or None, latents (B * T, 64, 16, 16))"""
         frames, v = self.frames_latents(batch)
