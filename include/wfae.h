@@ -1116,6 +1116,30 @@ int wfae_resae_join_bwd(const float* dy, const float* c2, const float* s2, const
 int wfae_resae_bn_running(const float* save_mean, const float* save_invstd, float* running_mean, float* running_var, int C,
                           float eps, float momentum, int64_t count, wfae_stream_t stream);
 
+/* ---- prediction / target / difference panels in the SEVIR VIL colours (csrc/panels.hip; reference
+ * pipeline/helpers.py:155-225 `log_wandb_images`).  Added within ABI version 103; nothing changed.
+ * panel_render: pred, target fp32 (B, T, H, W) contiguous; lut_vil, lut_diff: 256 x 3 device bytes (RGB), the colours of
+ *   the frame rows and of the difference row: the kernel holds no colour constants.  The first nb <= B samples are drawn,
+ *   samples >= nb are never read.  out: nb figures of wfae_panel_bytes(T, H, W, g) bytes each, one after the other.
+ *   A figure is Hfig = 3 H + 2 g rows of Wfig = T W + (T - 1) g pixels: row block 0 the target, 1 the prediction, 2 the
+ *   difference, each T panels of H x W in frame order; g white pixels (255, 255, 255) between neighbouring panels and
+ *   between row blocks.  It is written as the stream a PNG IDAT chunk holds before compression: Hfig scanlines, each a
+ *   filter byte 0 followed by 3 Wfig RGB bytes, so a figure is Hfig (1 + 3 Wfig) bytes.
+ *   Per pixel:  u(x) = (uint8)(min(max(x, 0), 1) * 255.0f), one fp32 multiply and a truncation toward zero, which is
+ *   (x.clamp(0, 1) * 255).numpy().astype('uint8'); u(NaN) = 0 (the reference's cast is unspecified there), u(-inf) = 0,
+ *   u(+inf) = 255.  d = |u(target) - u(pred)|.  Colours lut_vil[u(target)], lut_vil[u(pred)], lut_diff[d].
+ * panel_bytes: the bytes of one figure; 0 for arguments that panel_render refuses.
+ * range_count: *count (a device int64) = the number of the n elements of x with 0 <= x <= 1; NaN and +-inf are outside.
+ *   Integer partial counts in ws (wfae_range_count_workspace_bytes(n) bytes, 8-byte aligned), added by a second launch:
+ *   exact, so two launches give the same integer.
+ * Errors, all before any launch: null pointers WFAE_ERR_NULL_POINTER; a size < 1, nb < 1 or nb > B, g < 0, a figure of
+ *   2^31 bytes or more, n < 1 WFAE_ERR_BAD_SHAPE; a short or misaligned workspace WFAE_ERR_WORKSPACE. */
+size_t wfae_panel_bytes(int T, int H, int W, int g);
+int wfae_panel_render(const float* pred, const float* target, const uint8_t* lut_vil, const uint8_t* lut_diff, uint8_t* out,
+                      int B, int nb, int T, int H, int W, int g, wfae_stream_t stream);
+size_t wfae_range_count_workspace_bytes(int64_t n);
+int wfae_range_count(const float* x, int64_t n, int64_t* count, void* ws, size_t ws_bytes, wfae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,7 @@ class Model(tnn.Module):
         self.total_steps = cfg.trainer.total_train_steps
         self.global_step = 0
         self.current_epoch = 0
+        self.panels = None              # helpers.PanelSink with `--plots DIR` (rank 0): where the steps draw their figures
 
     def forward(self, x):
         return self.autoencoder(x)
@@ -132,7 +133,21 @@ class Model(tnn.Module):
         interval = max(1, int(self.cfg.logging.log_train_all_metrics_n * self.cfg.trainer.total_train_steps))
         if batch_idx % interval == 0:
             logs.update(helpers.log_metrics(pred.unsqueeze(2), inp.unsqueeze(2), "train"))
+        self._plot(pred, inp, "train", batch_idx)
         return aeloss, logs
+
+    def _plot(self, pred, inp, split, batch_idx):
+        """the figures of reference :220-222, :234-236, :250-252 (`log_wandb_images`), drawn only with `--plots` (`self.panels`) and when due:
+        (epoch * total + batch) against int(logging.log_train_plots_n * total), the train fraction in all three steps as
+        the reference has it, `total` the split's trainer.total_*_steps"""
+        if self.panels is None:
+            return
+        self.panels.global_step, self.panels.epoch = self.global_step, self.current_epoch
+        e, total = self.panels.epoch, self.panels.total(split)
+        label = {"train": "Train Reconstruction", "val": "Val_Reconstruction", "test": "Test_Reconstruction"}[split] \
+            + f" vs Original_epoch_{e}_batch_{batch_idx}" + ("_test" if split == "test" else "")
+        helpers.plot_panels(self, pred, inp, label, e * total + batch_idx,
+                            helpers.plot_fraction(self.cfg, "log_train_plots_n", 0.01), total)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx):
@@ -142,6 +157,7 @@ class Model(tnn.Module):
         aeloss, logs = self.loss(inp, pred, z, 0, self.get_last_layer(), "val", self.global_step)
         logs = dict(logs)
         logs.update(helpers.log_metrics(pred.unsqueeze(2), inp.unsqueeze(2), "val"))
+        self._plot(pred, inp, "val", batch_idx)
         return aeloss, logs
 
     @torch.no_grad()
@@ -154,6 +170,7 @@ class Model(tnn.Module):
         _, log_d = self.loss(inp, pred, z, 1, self.get_last_layer(), "test", self.global_step)
         logs.update(log_d)
         logs.update(helpers.log_metrics(pred.unsqueeze(2), inp.unsqueeze(2), "test"))
+        self._plot(pred, inp, "test", batch_idx)
         return logs
 
 
@@ -254,6 +271,9 @@ def main(argv=None):
     ap.add_argument("--model", choices=("tf", "lin"), default="tf",
                     help="tf = ae_64x8x8_tf (what the reference ae_v2/train.py:18 imports), lin = ae_64x8x8_lin (ae_v2_2)")
     ap.add_argument("--test", action="store_true", help="run the test loop after training (trainer.test)")
+    ap.add_argument("--plots", default=None, metavar="DIR",
+                    help="write target / prediction / difference panels of the training, validation and test steps, at "
+                         "the reference's cadence, into DIR as PNG files with one line each in DIR/index.jsonl (rank 0)")
     args, unknown = ap.parse_known_args(argv)
     cfg = C.load(args.config, CARRIED_KEYS)
     cli = C.from_dotlist(unknown)
@@ -314,6 +334,7 @@ def main(argv=None):
     torch.manual_seed(0)
     Fn._seed_counter[0] = 0          # the counter-based dropout stream restarts with the run (restored on --resume)
     model = Model(cfg, img_size=size, variant=args.model).to(dev).train()
+    model.panels = helpers.make_sink(args.plots, rank, cfg.trainer, total_steps, len(val_loader), len(test_loader))
     net, loss_fn = model.autoencoder, model.loss
     Fn.set_wgrad_overlap(True)
     opt, sched = model.configure_optimizers()

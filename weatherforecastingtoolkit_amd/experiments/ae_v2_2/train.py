@@ -115,6 +115,7 @@ class Model(tnn.Module):
         self.total_steps = cfg.trainer.total_train_steps
         self.accumulate_grad_batches = cfg.trainer.accumulate_grad_batches
         self.global_step = 0
+        self.panels = None              # helpers.PanelSink with `--plots DIR` (rank 0): where the steps draw their figures
         self._dp = None
         self.overlap_exchange = True    # generator all-reduce under the discriminator's forward / backward (training_step)
         self.on_after_backward = None   # optional callable(tag) run after each backward ("g" / "d"), like Lightning's hook
@@ -188,7 +189,21 @@ class Model(tnn.Module):
             # batch the reference's disc_start comparison still sees the count of G steps before the
             # discriminator starts, which is all the comparison needs here.
             self.global_step += 1
+        self._plot(pred, inp, "train", batch_idx)
         return pred, logs
+
+    def _plot(self, pred, inp, split, batch_idx):
+        """the figures of reference :165-167, :181-183, :197-199 (`log_wandb_images`), drawn only with `--plots` (`self.panels`) and when due:
+        (epoch * total + batch) against int(logging.log_train_plots_n * total), the train fraction in all three steps as
+        the reference has it, `total` the split's trainer.total_*_steps"""
+        if self.panels is None:
+            return
+        self.panels.global_step = self.global_step
+        e, total = self.panels.epoch, self.panels.total(split)
+        label = {"train": "Train Reconstruction", "val": "Val_Reconstruction", "test": "Test_Reconstruction"}[split] \
+            + f" vs Original_epoch_{e}_batch_{batch_idx}" + ("_test" if split == "test" else "")
+        helpers.plot_panels(self, pred, inp, label, e * total + batch_idx,
+                            helpers.plot_fraction(self.cfg, "log_train_plots_n", 0.01), total)
 
 
     def _g_step(self, logs, clip, started=False):
@@ -214,6 +229,7 @@ class Model(tnn.Module):
             _, log_d = self.loss(inp, pred, 1, self.get_last_layer(), split, self.global_step)
             logs.update(log_d)
         logs.update(helpers.log_metrics(pred.unsqueeze(2), inp.unsqueeze(2), split))
+        self._plot(pred, inp, split, batch_idx)
         return pred, logs
 
 
@@ -228,6 +244,9 @@ def main(argv=None):
                     help="reference: torch.set_float32_matmul_precision('high') (train.py main).  'medium' = BASELINE "
                          "config 5's regime and MORE than torch's meaning of the word: bf16 MFMA operands AND bf16 activation "
                          "storage in HBM (the counterpart of bf16 autocast); WFAE_BF16_STORAGE=0 keeps the tensors fp32")
+    ap.add_argument("--plots", default=None, metavar="DIR",
+                    help="write target / prediction / difference panels of the training step, at the reference's cadence, "
+                         "into DIR as PNG files with one line each in DIR/index.jsonl (rank 0)")
     add_lpips_arguments(ap)
     args, unknown = ap.parse_known_args(argv)
     cfg = C.load(args.config, CARRIED_KEYS)
@@ -260,6 +279,7 @@ def main(argv=None):
     model = Model(cfg, img_size=size, lpips=lpips_from_arguments(args)).to(dev).train()
     Fn.set_wgrad_overlap(True)
     model.configure_optimizers()
+    model.panels = helpers.make_sink(args.plots, rank, cfg.trainer, total, 0, 0)     # this driver has no other loop
 
     ckpt_dir = os.path.join(cfg.experiment_path, "outputs", cfg.experiment_name, "checkpoints")
     last = os.path.join(ckpt_dir, "last.ckpt")
@@ -292,6 +312,8 @@ def main(argv=None):
 
     while model.global_step < stop_at:
         first = (model.global_step * accum) % max(1, len(loader))
+        if model.panels is not None:
+            model.panels.epoch = (model.global_step * accum) // max(1, len(loader))
         for i in range(first, len(loader)):
             if model.global_step >= stop_at:
                 break

@@ -42,6 +42,9 @@ def main(argv=None):
     ap.add_argument("--presample", type=parse_presample, default="auto", metavar="auto|none|T,H,W",
                     help="with --data-dir: pool the events on the device as the loader converts them.  auto = (2, 3, 3) "
                          "when the config names sevirlr and the store holds raw 384x384x49 events, else none")
+    ap.add_argument("--plots", default=None, metavar="DIR",
+                    help="write target / prediction / difference panels of the training step, at the reference's cadence, "
+                         "into DIR as PNG files with one line each in DIR/index.jsonl (rank 0)")
     add_lpips_arguments(ap)
     args, unknown = ap.parse_known_args(argv)
     cfg = C.load(args.config, CARRIED_KEYS)
@@ -107,6 +110,7 @@ def main(argv=None):
     model = Model(cfg, img_size=size, lpips=lpips_from_arguments(args)).to(dev).train()
     Fn.set_wgrad_overlap(True)
     model.configure_optimizers()
+    model.panels = helpers.make_sink(args.plots, rank, cfg.trainer, total, 0, 0)      # this driver has no other loop
 
     t0, done, epoch = time.time(), 0, 0
     pending = []   # per-step scalars are read one step late (no stall of the launch queue)
@@ -120,6 +124,8 @@ def main(argv=None):
 
     while model.global_step < total:
         loader.set_epoch(epoch)              # this epoch's permutation and this epoch's transforms
+        if model.panels is not None:
+            model.panels.epoch = epoch
         for k in range(per_epoch):
             if model.global_step >= total:
                 break

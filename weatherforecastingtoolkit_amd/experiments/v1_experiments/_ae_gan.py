@@ -421,12 +421,27 @@ class Model(Step, tnn.Module):
             raise WfaeError("Model.training_step: call configure_optimizers() first")
         self.autoencoder.train()        # the shared driver leaves `autoencoder` attributes in evaluation mode
         inp = self.frames(batch)
-        rec = Fn.l1_loss(self(inp), inp, float(self.recon_weight))
+        pred = self(inp)
+        rec = Fn.l1_loss(pred, inp, float(self.recon_weight))
         loss, gn = self.optimizer_step(rec)
         self.logs = {"train/total_loss": loss, "train/rec_loss": loss, "train/g_loss": 0.0, "train/d_weight": 0.0,
                      "train/g_grad_norm": gn}
         self.global_step += 1
+        if self.panels is not None:
+            self._plot(pred, inp, "train", self.panels.batch_idx)
         return loss, gn
+
+    def _plot(self, pred, inp, split, batch_idx):
+        """the figures of reference :478-480, :493-495, :508-510: the batch index against int(fraction * total), the train fraction and total in
+        the training step, the validation ones in the validation AND the test step"""
+        if self.panels is None:
+            return
+        e, tr = self.panels.epoch, split == "train"
+        label = {"train": "Train Reconstruction", "val": "Val_Reconstruction", "test": "Test_Reconstruction"}[split] \
+            + f" vs Original_epoch_{e}_batch_{batch_idx}" + ("_test" if split == "test" else "")
+        helpers.plot_panels(self, pred, inp, label, batch_idx,
+                            helpers.plot_fraction(self.cfg, "log_train_plots_n" if tr else "log_val_plots_n", 0.1),
+                            self.panels.total("train" if tr else "val"))
 
     def configure_optimizers(self):
         if not self.trainable:
@@ -442,6 +457,7 @@ class Model(Step, tnn.Module):
         rec = Fn.l1_loss(pred, inp, float(self.recon_weight))
         logs = {f"{split}/total_loss": rec, f"{split}/rec_loss": rec, f"{split}/g_loss": 0.0, f"{split}/d_weight": 0.0}
         logs.update(helpers.log_metrics(pred.unsqueeze(2), inp.unsqueeze(2), split))
+        self._plot(pred, inp, split, batch_idx)
         return rec, logs
 
     def test_step(self, batch, batch_idx=0):

@@ -165,7 +165,21 @@ class Model(Step, tnn.Module):
             self.d_opt.zero_grad(set_to_none=True)
         self.global_step += 1
         self.logs = logs
+        if self.panels is not None:
+            self._plot(pred, x, "train", self.panels.batch_idx)
         return aeloss.detach(), gn
+
+    def _plot(self, pred, inp, split, batch_idx):
+        """the figures of reference :196-198, :211-213, :226-228: the batch index against int(fraction * total), the train fraction and total in
+        the training step, the validation ones in the validation AND the test step"""
+        if self.panels is None:
+            return
+        e, tr = self.panels.epoch, split == "train"
+        label = {"train": "Train Reconstruction", "val": "Val_Reconstruction", "test": "Test_Reconstruction"}[split] \
+            + f" vs Original_epoch_{e}_batch_{batch_idx}" + ("_test" if split == "test" else "")
+        helpers.plot_panels(self, pred, inp, label, batch_idx,
+                            helpers.plot_fraction(self.cfg, "log_train_plots_n" if tr else "log_val_plots_n", 0.1),
+                            self.panels.total("train" if tr else "val"))
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0, split="val"):
@@ -177,6 +191,7 @@ class Model(Step, tnn.Module):
         logs = dict(logs)
         logs.update(self.loss(x, pred, post, 1, self.get_last_layer(), split, self.global_step)[1])
         logs.update(helpers.log_metrics(pred.unsqueeze(2), x.unsqueeze(2), split))
+        self._plot(pred, x, split, batch_idx)
         return aeloss, logs
 
     def test_step(self, batch, batch_idx=0):

@@ -301,8 +301,14 @@ class Model(Step, tnn.Module):
         logs.update(log_d)
         ae = self.autoencoder
         if frames is not None and getattr(ae, "can_decode", lambda: False)():
-            logs.update(helpers.log_metrics(ae.decode(pred.view(frames.shape[0], frames.shape[1], *LATENT_SHAPE)), frames,
-                                            split))
+            decoded_pred = ae.decode(pred.view(frames.shape[0], frames.shape[1], *LATENT_SHAPE))
+            logs.update(helpers.log_metrics(decoded_pred, frames, split))
+            if self.panels is not None:
+                # reference :295-297 (the train fraction and total, as it has them); it has no test step: the port's takes
+                # the validation label with `_test` appended
+                label = f"Reconstruction vs Original_epoch_{self.panels.epoch}_batch_{batch_idx}"
+                helpers.plot_panels(self, decoded_pred, frames, label + ("_test" if split == "test" else ""), batch_idx,
+                                    helpers.plot_fraction(self.cfg, "log_train_plots_n", 0.001), self.panels.total("train"))
         return aeloss, logs
 
     def test_step(self, batch, batch_idx=0):

@@ -307,7 +307,7 @@ class Model(Step, tnn.Module):
         return self.optimizer_step(loss)
 
     @torch.no_grad()
-    def validation_step(self, batch, batch_idx=0, split="val"):
+    def validation_step(self, batch, batch_idx=0, split="val", plot_idx=None):
         """-> (loss, logs): logs holds `{split}_loss` and, for a batch of frames with a provider that decodes, the
         `{split}_` calc_metrics keys of the decoded reconstruction against the input frames (reference :214-217)"""
         frames, v = self.frames_latents(batch)
@@ -316,8 +316,15 @@ class Model(Step, tnn.Module):
         ae = self.autoencoder
         if frames is not None and batch_idx % self._metric_interval(split) == 0 \
                 and getattr(ae, "can_decode", lambda: False)():
-            logs.update(helpers.log_metrics(ae.decode(pred), frames, split))
+            decoded_pred = ae.decode(pred)
+            logs.update(helpers.log_metrics(decoded_pred, frames, split))
+            if self.panels is not None:
+                # reference :219-221; it has no test step: the port's takes the validation label with `_test` appended
+                i = batch_idx if plot_idx is None else plot_idx
+                label = f"Val_Reconstruction vs Original_epoch_{self.panels.epoch}_batch_{i}"
+                helpers.plot_panels(self, decoded_pred, frames, label + ("_test" if split == "test" else ""), i,
+                                    helpers.plot_fraction(self.cfg, "log_val_plots_n", 0.05), self.panels.total("val"))
         return loss, logs
 
     def test_step(self, batch, batch_idx=0):
-        return self.validation_step(batch, 0, split="test")
+        return self.validation_step(batch, 0, split="test", plot_idx=batch_idx)

@@ -196,10 +196,17 @@ class Model(Step, tnn.Module):
     """reference Model (:137-239): `predictor`, `forward`, the training / validation / test steps; the optimiser is
     `Step`'s"""
 
-    def __init__(self, cfg, autoencoder=None):
+    # how each reference script words and times its validation / test figures (`log_wandb_images`):
+    # style -> (counts epochs into the counter, config key of the fraction, test label prefix, test label suffix)
+    PLOT_STYLES = {"ind": (True, "log_train_plots_n", "", "_test"),            # pretrained_ae_dlinear_ind :201-203, :226-228
+                   "sevir": (False, "log_val_plots_n", "", "_test"),           # pretrained_ae_dlinear_sevir :200-202, :225-227
+                   "indc_indp": (False, "log_val_plots_n", "Test_", "")}       # ..._indc_indp :200-202, :226-228
+
+    def __init__(self, cfg, autoencoder=None, plots="sevir"):
         super().__init__()
         self.cfg = cfg
         self.autoencoder = autoencoder
+        self.plot_style = self.PLOT_STYLES[plots]
         self.input_frames, self.pred_frames = cfg.dataset.input_frames, cfg.dataset.pred_frames
         self.total_steps = cfg.trainer.total_train_steps
         self.predictor = DLinear(cfg.dlinear)
@@ -264,7 +271,17 @@ class Model(Step, tnn.Module):
             shape = (b, self.pred_frames, c, h, w)
             fc = ops.dlinear_forecast(pred, rows, L, f).view(shape)
             tgt = ops.dlinear_forecast(ops.dlinear_target(rows, L, P, f), rows, L, f).view(shape)
-            logs.update(helpers.log_metrics(ae.decode(fc), ae.decode(tgt), split))
+            decoded_pred, decoded_tgt = ae.decode(fc), ae.decode(tgt)
+            logs.update(helpers.log_metrics(decoded_pred, decoded_tgt, split))
+            if self.panels is not None:
+                epochs, key, prefix, suffix = self.plot_style
+                e, tv = self.panels.epoch, self.panels.total("val")     # every script times both splits by total_val_steps
+                if split != "test":
+                    prefix = suffix = ""
+                helpers.plot_panels(self, decoded_pred, decoded_tgt,
+                                    f"{prefix}Reconstruction vs Original_epoch_{e}_batch_{batch_idx}{suffix}",
+                                    e * tv + batch_idx if epochs else batch_idx,
+                                    helpers.plot_fraction(self.cfg, key, 0.05), tv)
         return loss, logs
 
     def test_step(self, batch, batch_idx=0):

@@ -34,6 +34,7 @@ class Step:
     preamble, `autoencoder` of the class it is mixed into."""
 
     trained = "predictor"        # the attribute that holds the trained sub-module
+    panels = None                # helpers.PanelSink with `--plots DIR` on rank 0: the steps that plot draw into it
     exact_complements = False    # see optim.FusedAdamW
 
     def configure_optimizers(self):
@@ -199,6 +200,9 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
                     help="run the validation pass on synthetic events too (with --data-dir it always runs)")
     ap.add_argument("--test", action="store_true", help="run the test loop after the fit")
     ap.add_argument("--resume", action="store_true", help="continue from last.ckpt if there is one")
+    ap.add_argument("--plots", default=None, metavar="DIR",
+                    help="write target / prediction / difference panels of the steps that plot in the reference into "
+                         "DIR as PNG files, with one line per figure in DIR/index.jsonl (rank 0)")
     ap.add_argument("--stop-after", type=int, default=-1,
                     help="stop (and checkpoint) after this many optimiser steps without changing the schedule: an "
                          "interrupted run that --resume continues")
@@ -226,10 +230,15 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
     model = build(cfg, size).to(dev).train()
     if getattr(model, "autoencoder", None) is not None:
         model.autoencoder.eval()
+    # the figures' sink: rank 0's, and only with --plots; a model's steps draw nothing while `panels` is None
+    model.panels = helpers.make_sink(args.plots, rank, cfg.trainer, total, len(loader) if mode == "test" else len(val),
+                                     len(loader) if mode == "test" else len(test))
     step = 0
     if mode == "test":
         model.eval()
         for i in range(min(total, len(loader))):
+            if model.panels is not None:
+                model.panels.global_step = step
             loss, logs = model.test_step(_frames(loader[i]), step)
             step += 1
             if rank == 0:
@@ -265,6 +274,8 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
         for i in range(first, nb):
             if step >= stop_at:
                 break
+            if model.panels is not None:
+                model.panels.global_step, model.panels.epoch, model.panels.batch_idx = step, step // nb, i
             loss, gn = model.training_step(_frames(loader[i]))
             step += 1
             if rank == 0 and step % max(1, cfg.trainer.log_every_n_steps) == 0:
@@ -275,13 +286,15 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
                 save_checkpoint(last, model, state, step, step // nb)
         if validating and step % nb == 0 and step < total:
             # the validation loop at the end of every training epoch; the one after the last step follows the checkpoint
-            report(evaluate(model, val, "val", cfg.trainer.limit_val_batches, world), rank, step=step, epoch=(step - 1) // nb)
+            report(evaluate(model, val, "val", cfg.trainer.limit_val_batches, world, step, nb), rank, step=step,
+                   epoch=(step - 1) // nb)
     if rank == 0:
         save_checkpoint(last, model, state, step, step // nb)
     if validating and step >= total:
-        report(evaluate(model, val, "val", cfg.trainer.limit_val_batches, world), rank, step=step, epoch=(step - 1) // nb)
+        report(evaluate(model, val, "val", cfg.trainer.limit_val_batches, world, step, nb), rank, step=step,
+               epoch=(step - 1) // nb)
     if args.test:
-        report(evaluate(model, test, "test", cfg.trainer.limit_test_batches, world), rank)
+        report(evaluate(model, test, "test", cfg.trainer.limit_test_batches, world, step, nb), rank)
     if rank == 0:
         print("done")
     return 0
@@ -382,11 +395,12 @@ def synthetic_data(cfg, layout, mode, validate, test, device, rank, world):
     return loader, extra(4321) if validate else (), extra(9876) if test else (), size
 
 
-def evaluate(model, loader, split, limit, world):
+def evaluate(model, loader, split, limit, world, step=None, nb_train=1):
     """one pass over `limit` (a fraction, Lightning's limit_*_batches; None = all) of `loader` in evaluation mode ->
     {key: epoch mean of the step's logs (`_mean_logs`), "batches": n}, or {"skipped": reason} where the model has no
     step for `split` or refuses it now.  Every module gets its own train / eval state back, so a frozen provider stays
-    in evaluation mode; the generators and the dropout counter are left where they were, so a pass does not move the run"""
+    in evaluation mode; the generators and the dropout counter are left where they were, so a pass does not move the run.
+    `step`, `nb_train`: the run's optimiser step and batches per epoch, for the sink of `--plots` (index lines, labels)"""
     name = "test_step" if split == "test" else "validation_step"
     if not hasattr(model, name):
         return {"skipped": f"{type(model).__module__}.Model has no {name}"}
@@ -399,6 +413,8 @@ def evaluate(model, loader, split, limit, world):
     n = n if limit is None else max(1, int(n * limit)) if n else 0
     modes = [(m, m.training) for m in model.modules()]
     counter = Fn._seed_counter[0]
+    if getattr(model, "panels", None) is not None and step is not None:
+        model.panels.global_step, model.panels.epoch = step, max(0, step - 1) // max(1, nb_train)
     model.eval()
     rows = []
     with torch.random.fork_rng(devices=[torch.cuda.current_device()] if torch.cuda.is_available() else []):

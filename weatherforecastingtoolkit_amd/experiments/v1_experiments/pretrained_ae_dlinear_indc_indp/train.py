@@ -8,6 +8,7 @@ series_decomp are shared by the three DLinear experiments (../_dlinear.py); the 
 """
 from __future__ import annotations
 
+import functools
 import os
 import sys
 
@@ -18,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def main(argv=None):
-    return run(HERE, argv, with_provider(Model), default_mode="fit")
+    return run(HERE, argv, with_provider(functools.partial(Model, plots="indc_indp")), default_mode="fit")
 
 
 if __name__ == "__main__":

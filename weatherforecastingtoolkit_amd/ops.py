@@ -2820,3 +2820,44 @@ def resae_bn_stats_train(x, gamma, beta, running_mean, running_var, eps=1e-5, mo
     _call("wfae_resae_bn_running", 0, 16 * c, _p(st.mean), _p(st.invstd), _p(running_mean), _p(running_var), c, eps, momentum,
           nb * h * wd * replicas, _stream())
     return st
+
+
+# ---- prediction / target / difference panels (include/wfae.h "panels in the SEVIR VIL colours"; csrc/panels.hip)
+def panel_bytes(t, h, w, gap=0):
+    """bytes of one figure of `t` frames of h x w with `gap` white pixels between panels: (3h + 2 gap) scanlines of a
+    filter byte and 3 (t w + (t - 1) gap) colour bytes; 0 where panel_render refuses the arguments"""
+    return int(_lib.load().wfae_panel_bytes(int(t), int(h), int(w), int(gap)))
+
+
+def panel_render(pred, target, lut_vil, lut_diff, nb, gap=0):
+    """pred, target fp32 (B, T, H, W); lut_vil, lut_diff uint8 (256, 3) on the same device -> uint8 (nb, Hfig, 1 + 3 Wfig):
+    the first nb samples as target / prediction / difference rows, each figure the uncompressed scanlines of a PNG"""
+    _chk(pred, target)
+    if pred.dim() != 4 or pred.shape != target.shape:
+        raise _lib.WfaeError(f"panel_render: pred {tuple(pred.shape)} and target {tuple(target.shape)} must be one "
+                             "(B, T, H, W) shape")
+    for name, lut in (("lut_vil", lut_vil), ("lut_diff", lut_diff)):
+        if (lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3) or not lut.is_contiguous()
+                or lut.device != pred.device):
+            raise _lib.WfaeError(f"panel_render: {name} must be a contiguous uint8 (256, 3) tensor on {pred.device}")
+    b, t, h, w = pred.shape
+    nb, gap = int(nb), int(gap)
+    fig = panel_bytes(t, h, w, gap) if min(b, t, h, w) > 0 else 0
+    if not 1 <= nb <= b or gap < 0 or fig == 0:
+        raise _lib.WfaeError(f"panel_render: {nb} samples of a batch of shape {tuple(pred.shape)} with gap {gap}")
+    hfig, wfig = 3 * h + 2 * gap, t * w + (t - 1) * gap
+    out = torch.empty((nb, hfig, 1 + 3 * wfig), dtype=torch.uint8, device=pred.device)
+    _call("wfae_panel_render", 0, nb * (fig + 8 * t * h * w), _p(pred), _p(target), lut_vil.data_ptr(), lut_diff.data_ptr(),
+          out.data_ptr(), b, nb, t, h, w, gap, _stream())
+    return out
+
+
+def range_count(x):
+    """the number of elements of the fp32 tensor x in [0, 1] (NaN, +-inf outside) -> int64 device scalar"""
+    _chk(x)
+    if x.numel() < 1:
+        raise _lib.WfaeError("range_count: empty tensor")
+    out = torch.empty((), dtype=torch.int64, device=x.device)
+    ws = workspace()
+    _call("wfae_range_count", 0, 4 * x.numel(), _p(x), x.numel(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return out

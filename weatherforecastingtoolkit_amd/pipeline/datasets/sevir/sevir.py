@@ -26,6 +26,21 @@ from torch.utils.data import random_split
 
 from ..sevire.sevir import _M64, SEVIRFrameLoader, _mix64, lr_presample  # noqa: F401  (lr_presample: for the callers)
 
+# the SEVIR VIL colour scale as runs of byte values: (first value of the run, (R, G, B)); a run ends where the next begins
+VIL_RUNS = ((0, (77, 77, 77)), (16, (40, 190, 40)), (31, (25, 150, 25)), (59, (10, 105, 10)), (74, (10, 75, 10)),
+            (100, (245, 245, 0)), (133, (237, 172, 0)), (160, (240, 110, 0)), (181, (160, 0, 0)), (219, (231, 0, 255)))
+
+
+def vil_lut():
+    """The reference's `vil_cmap()` (:1237-1268) in table form: uint8 (256, 3), row v the RGB that
+    `imshow(u8, cmap=cmap, norm=norm)` paints for the byte value v, i.e. `cmap(norm(v), bytes=True)[:, :3]` of its
+    ListedColormap + BoundaryNorm(VIL_LEVELS, 10).  Ten runs; value 255 takes the "over" colour, which the reference sets
+    to the last bin's.  tests/golden/g23_panel_luts.npz holds the table as matplotlib evaluates it."""
+    lut = torch.empty((256, 3), dtype=torch.uint8)
+    for (start, rgb), (end, _) in zip(VIL_RUNS, VIL_RUNS[1:] + ((256, None),)):
+        lut[start:end] = torch.tensor(rgb, dtype=torch.uint8)
+    return lut
+
 
 class SequenceBatchLoader(SEVIRFrameLoader):
     """Batches of `batch_size` single sequences in a given order of global sequence indices (`order`), the last one
