@@ -7,6 +7,7 @@ through ctypes.  All tensors must be CUDA(HIP) fp32 and contiguous (NCHW).
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import torch
@@ -2137,10 +2138,19 @@ def lpips_prep_bwd(dy, scale, cx):
     return dx
 
 
+def _chk_planes(what, a, b):
+    """the two images of an image metric: one shape, (N, ..., H, W)"""
+    if a.shape != b.shape:
+        raise _lib.WfaeError(f"{what}: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    if a.dim() < 3:
+        raise _lib.WfaeError(f"{what}: expected (N, ..., H, W), got {tuple(a.shape)}")
+
+
 def ssim_fwd(x, y, clamp01=False):
     _chk(x, y)
-    nb = x.shape[0] * x.shape[1]
+    _chk_planes("ssim_fwd", x, y)
     h, wd = x.shape[-2:]
+    nb = math.prod(x.shape[:-2])
     out = torch.empty((), dtype=torch.float32, device=x.device)
     ws = workspace()
     _call("wfae_ssim_fwd", 0, 8 * x.numel(), _p(x), _p(y), _p(out), nb, h, wd, int(clamp01), ws.data_ptr(), ws.numel(), _stream())
@@ -2149,8 +2159,9 @@ def ssim_fwd(x, y, clamp01=False):
 
 def ssim_bwd(x, y, gout):
     _chk(x, y, gout)
-    nb = x.shape[0] * x.shape[1]
+    _chk_planes("ssim_bwd", x, y)
     h, wd = x.shape[-2:]
+    nb = math.prod(x.shape[:-2])
     dy = torch.empty_like(y)
     ws = workspace(3 * nb * (h - 10) * (wd - 10) * 4)
     _call("wfae_ssim_bwd", 0, 12 * x.numel(), _p(x), _p(y), _p(gout), _p(dy), nb, h, wd, ws.data_ptr(), ws.numel(), _stream())
@@ -2159,6 +2170,7 @@ def ssim_bwd(x, y, gout):
 
 def psnr(pred, target, clamp01=False):
     _chk(pred, target)
+    _chk_planes("psnr", pred, target)
     nb = pred.shape[0]
     hw = pred.numel() // nb
     out = torch.empty((), dtype=torch.float32, device=pred.device)
