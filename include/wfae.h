@@ -685,7 +685,11 @@ int wfae_huber_bwd(const float* pred, const float* target, const float* gloss, f
  *   (tok (N, S, C) + res (N, C, S) (may be null)) * mul.  C and S multiples of 32.
  * softmax: y[row] = softmax(scale * x[row]) over `cols` (in place allowed).
  * posterior: moments (N, 2C, HW) -> mean, logvar = clamp(., -30, 20), std = exp(logvar / 2), and — when noise and
- *   sample are given — sample = mean + std * noise, all (N, C, HW). */
+ *   sample are given — sample = mean + std * noise, all (N, C, HW).
+ * posterior_seq (added for experiments/ae_s2, within ABI version 103; nothing changed): the sample alone for a frame
+ *   sequence.  moments (B * T, 2C, HW) with frame f = b * T + t, noise (T, B, C, HW) — draw t is the noise of frame t of
+ *   every sequence — -> z (B, T, C, HW), the bits of posterior's sample for the same element; mean, logvar and std are not
+ *   written.  16-byte accesses when HW % 4 == 0 and the three pointers are 16-byte aligned, else scalar. */
 size_t wfae_aekl_conv3_pack_bytes(int Cout, int Cin, int mode);
 int wfae_aekl_conv3_pack(const float* w, void* packed, int Cout, int Cin, int mode, wfae_stream_t stream);
 int wfae_aekl_conv3_fwd(const float* x, const void* packed, const float* bias, const float* gn_scale, const float* gn_shift,
@@ -701,6 +705,8 @@ int wfae_aekl_from_tokens(const float* tok, const float* res, float* y, int N, i
 int wfae_aekl_softmax(const float* x, float* y, int64_t rows, int cols, float scale, wfae_stream_t stream);
 int wfae_aekl_posterior(const float* moments, const float* noise, float* mean, float* logvar, float* std_, float* sample, int N,
                         int C, int HW, wfae_stream_t stream);
+int wfae_aekl_posterior_seq(const float* moments, const float* noise, float* z, int B, int T, int C, int HW,
+                            wfae_stream_t stream);
 
 /* ---- AutoencoderKL backward (csrc/aekl_bwd.hip): what `AutoencoderKL.unfreeze()` trains with.  NCHW fp32, fixed summation
  * order, no atomics: two launches give the same bits.  Added within ABI version 103; nothing changed.

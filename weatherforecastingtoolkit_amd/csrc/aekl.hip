@@ -399,6 +399,36 @@ __global__ __launch_bounds__(256) void aekl_posterior_kernel(const float* __rest
   if (sample) sample[i] = fmaf(sd, noise[i], mu);
 }
 
+// z (B, T, C, HW) of a frame sequence: frame f = b * T + t of the moments (B * T, 2C, HW) with the noise of draw t,
+// noise (T, B, C, HW) — the sample of aekl_posterior_kernel, expression and order, and nothing else written.  VEC = 4:
+// one 16-byte access per operand (CHW a multiple of 4, so a group of four never crosses a frame); VEC = 1: scalar.
+template <int VEC>
+__global__ __launch_bounds__(256) void aekl_posterior_seq_kernel(const float* __restrict__ mom, const float* __restrict__ noise,
+                                                                 float* __restrict__ z, int B, int T, long CHW, long total) {
+  const long stride = (long)gridDim.x * blockDim.x * VEC;
+  for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC; i < total; i += stride) {
+    const long f = i / CHW, r = i - f * CHW;
+    const long b = f / T, t = f - b * T;
+    const float* pm = mom + f * 2 * CHW + r;
+    const float* pn = noise + (t * B + b) * CHW + r;
+    if constexpr (VEC == 4) {
+      const float4 mu = *reinterpret_cast<const float4*>(pm);
+      const float4 lr = *reinterpret_cast<const float4*>(pm + CHW);
+      const float4 nz = *reinterpret_cast<const float4*>(pn);
+      float4 o;
+      o.x = fmaf(expf(0.5f * fminf(fmaxf(lr.x, -30.0f), 20.0f)), nz.x, mu.x);
+      o.y = fmaf(expf(0.5f * fminf(fmaxf(lr.y, -30.0f), 20.0f)), nz.y, mu.y);
+      o.z = fmaf(expf(0.5f * fminf(fmaxf(lr.z, -30.0f), 20.0f)), nz.z, mu.z);
+      o.w = fmaf(expf(0.5f * fminf(fmaxf(lr.w, -30.0f), 20.0f)), nz.w, mu.w);
+      *reinterpret_cast<float4*>(z + i) = o;
+    } else {
+      const float lv = fminf(fmaxf(pm[CHW], -30.0f), 20.0f);
+      const float sd = expf(0.5f * lv);
+      z[i] = fmaf(sd, *pn, *pm);
+    }
+  }
+}
+
 inline bool mode_ok(int mode) { return mode == MODE_BF16 || mode == MODE_SPLIT3 || mode == MODE_F32; }
 inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -543,6 +573,22 @@ int wfae_aekl_posterior(const float* moments, const float* noise, float* mean, f
   hipLaunchKernelGGL(aekl_posterior_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, moments, noise,
                      mean, logvar, std_, sample, CHW, total);
   return check_launch("aekl_posterior");
+}
+
+int wfae_aekl_posterior_seq(const float* moments, const float* noise, float* z, int B, int T, int C, int HW, wfae_stream_t stream) {
+  WFAE_REQUIRE(moments && noise && z, WFAE_ERR_NULL_POINTER, "aekl_posterior_seq: null pointer");
+  WFAE_REQUIRE(B > 0 && T > 0 && C > 0 && HW > 0, WFAE_ERR_BAD_SHAPE, "aekl_posterior_seq: bad shape B=%d T=%d C=%d HW=%d", B, T, C,
+               HW);
+  const long CHW = (long)C * HW, total = CHW * B * T;
+  WFAE_REQUIRE(total < (1l << 39), WFAE_ERR_BAD_SHAPE, "aekl_posterior_seq: too large");
+  const bool vec = HW % 4 == 0 && ((uintptr_t)moments | (uintptr_t)noise | (uintptr_t)z) % 16 == 0;
+  const long items = vec ? total / 4 : total;
+  const unsigned grid = (unsigned)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);     // 8 blocks per CU; grid-stride beyond
+  if (vec)
+    hipLaunchKernelGGL(aekl_posterior_seq_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, moments, noise, z, B, T, CHW, total);
+  else
+    hipLaunchKernelGGL(aekl_posterior_seq_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, moments, noise, z, B, T, CHW, total);
+  return check_launch("aekl_posterior_seq");
 }
 
 }  // extern "C"

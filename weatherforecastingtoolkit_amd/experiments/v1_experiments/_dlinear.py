@@ -254,6 +254,10 @@ class Model(Step, tnn.Module):
     def training_step(self, batch, batch_idx=0):
         """batch: frames (B,T,H,W) fp32 in [0,1] ('NTHW') or latents (B,T,C,h,w); AdamW + cosine warmup, clip 1.0"""
         _, v = self.frames_latents(batch)
+        return self.train_latents(v)
+
+    def train_latents(self, v):
+        """training_step on latents (B, T, C, h, w)"""
         loss, _, _ = self.latent_loss(v)
         return self.optimizer_step(loss)
 
@@ -262,6 +266,11 @@ class Model(Step, tnn.Module):
         """-> (loss, logs): logs holds `{split}_loss` and, when the provider decodes, the `{split}_` calc_metrics keys
         of the decoded forecast against the decoded target (reference :180-203)"""
         _, v = self.frames_latents(batch)
+        return self.validate_latents(v, batch_idx, split)
+
+    @torch.no_grad()
+    def validate_latents(self, v, batch_idx=0, split="val"):
+        """validation_step on latents (B, T, C, h, w)"""
         loss, pred, rows = self.latent_loss(v)
         logs = {f"{split}_loss": loss}
         ae = self.autoencoder

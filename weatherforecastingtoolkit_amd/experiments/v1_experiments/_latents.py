@@ -8,6 +8,7 @@ from __future__ import annotations
 import torch
 import torch.nn as tnn
 
+from ... import ops
 from ..._lib import WfaeError
 from ...pipeline.models.ae_64x8x8_lin import PosAwareAE_TF
 
@@ -21,7 +22,9 @@ class Autoencoder(tnn.Module):
     from the `autoencoder:` config block `cfg` (the reference's keys), with `cfg.checkpoint` loaded when given (a state
     dict, or a Lightning checkpoint that holds it under the `autoencoder.` / `model.` prefix, other modules' keys next to
     it being ignored), else a seeded initialisation
-    (`cfg.seed`, default 0).  encode returns the posterior's mode; frames go through in chunks of `cfg.chunk_frames`.
+    (`cfg.seed`, default 0).  encode returns the posterior's mode; frames go through in chunks of `cfg.chunk_frames`
+    (default 8; 0 = all B*T frames in one pass).  With `cfg.sample: true` (ae_s2) encode returns a sample instead,
+    z = mean + std * noise, the noise drawn as the reference's loop over T draws it (`draw_noise`).
     kind "ae_gan.convautoencoder": the residual `ConvAutoencoderBIG` of ae_gan in evaluation mode (`cfg.latent_dim`, default
     2048; `cfg.checkpoint` / `cfg.seed` as for autoencoder_kl): encode (B, T, 1, 128, 128) -> (B, T, latent_dim, 1, 1), decode
     back to frames, the raw `final_conv` output as in the reference; frames go through in chunks of `cfg.chunk_frames`
@@ -36,10 +39,13 @@ class Autoencoder(tnn.Module):
         super().__init__()
         self.kind = kind
         self.chunk_frames = 0
+        self.sample = False
         if kind == "autoencoder_kl":
             self.autoencoder = self._build_autoencoder_kl(cfg or {})
-            self.chunk_frames = int((cfg or {}).get("chunk_frames") or 8)
-            if self.chunk_frames < 1:
+            chunk = (cfg or {}).get("chunk_frames")
+            self.chunk_frames = 8 if chunk is None else int(chunk)      # 0: all B*T frames in one pass
+            self.sample = bool((cfg or {}).get("sample") or False)
+            if self.chunk_frames < 0:
                 raise ValueError(f"autoencoder.chunk_frames={self.chunk_frames}")
         elif kind == "ae_gan.convautoencoder":
             self.autoencoder = self._build_ae_gan(cfg or {})
@@ -92,10 +98,31 @@ class Autoencoder(tnn.Module):
         n = self.chunk_frames if self.chunk_frames > 0 else frames.shape[0]
         return [frames[i:i + n].contiguous() for i in range(0, frames.shape[0], n)]
 
+    def draw_noise(self, b, t, latent_shape, device, generator=None):
+        """(T, B, C, h, w): the T draws torch.randn((B, C, h, w)) of the reference's per-frame `encode(frame).sample()`
+        (ae_s2/train.py:34-37), in frame order from `generator` (None: the device's global generator), each written into
+        its slice of one buffer.  One large draw is not the same stream."""
+        noise = torch.empty((t, b, *latent_shape), dtype=torch.float32, device=device)
+        for i in range(t):
+            torch.randn((b, *latent_shape), generator=generator, device=device, dtype=torch.float32, out=noise[i])
+        return noise
+
     @torch.no_grad()
-    def encode(self, x):
+    def encode(self, x, generator=None, noise=None):
+        """x (B, T, 1, H, W) -> (B, T, C, h, w).  `generator` / `noise` (T, B, C, h, w) belong to `sample: true`: `noise`
+        replaces the draw"""
         b, t, c, h, w = x.shape
         frames = x.reshape(b * t, c, h, w)
+        if not self.sample and (generator is not None or noise is not None):
+            raise WfaeError("Autoencoder.encode: generator / noise need the sampled provider (autoencoder_kl with sample: true)")
+        if self.kind == "autoencoder_kl" and self.sample:
+            moments = torch.cat([self.autoencoder.moments(f) for f in self._chunks(frames)])
+            shape = (moments.shape[1] // 2, *moments.shape[2:])
+            if noise is None:
+                noise = self.draw_noise(b, t, shape, moments.device, generator)
+            elif tuple(noise.shape) != (t, b, *shape):
+                raise WfaeError(f"Autoencoder.encode: noise {tuple(noise.shape)}, expected {(t, b, *shape)}")
+            return ops.aekl_posterior_seq(moments, noise.contiguous())
         if self.kind == "autoencoder_kl":
             z = torch.cat([self.autoencoder.encode(f).mode() for f in self._chunks(frames)])
         elif self.kind == "ae_gan.convautoencoder":

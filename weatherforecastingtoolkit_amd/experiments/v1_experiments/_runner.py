@@ -19,7 +19,7 @@ import torch
 
 from ... import config as C
 from ... import functional as Fn
-from ... import parallel, synth
+from ... import ops, parallel, synth
 from ..._lib import WfaeError
 from ...pipeline import helpers
 from ...pipeline.datasets.sevir.sevir import SEVIRLightningDataModule
@@ -40,7 +40,9 @@ class Step:
     def configure_optimizers(self):
         o, sp = self.cfg.optim, self.cfg.cosine_warmup
         net = getattr(self, self.trained)
-        self.opt = helpers.adamw_optimizer(net, o.lr, o.weight_decay, exact_complements=self.exact_complements)
+        # optim.beta1 / beta2: ae_s2's config names them (reference ae_s2/train.py:220-221); the defaults are AdamW's
+        self.opt = helpers.adamw_optimizer(net, o.lr, o.weight_decay, beta1=o.get("beta1", 0.9), beta2=o.get("beta2", 0.999),
+                                           exact_complements=self.exact_complements)
         self.sch = helpers.cosine_warmup_scheduler(self.opt, sp.start_lr, sp.final_lr, sp.peak_lr, self.total_steps,
                                                    sp.warmup_ratio * self.total_steps)
         self._dp = parallel.DataParallelTrainer(net, self.opt)
@@ -178,14 +180,15 @@ RATES = {"sequences_per_s": lambda d: d.batch_size, "frames_per_s": lambda d: d.
 
 
 def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate="sequences_per_s",
-        state=predictor_state):
+        state=predictor_state, test_after_fit=False):
     """driver of an experiment in directory `here`, on synthetic blob events or with `--data-dir` on a SEVIR store: `fit`
     trains `build(cfg, size)` (AdamW, cosine warmup, clip), prints a JSON line every trainer.log_every_n_steps steps and
     writes `last.ckpt` with `state(model)` and the resume state; `--mode test` — offered only where `default_mode` is
     given — runs test_step over the loader (the test split of a store).  With `--data-dir` or `--validate` a validation
     pass follows every training epoch and the last step; `--test` adds a test pass after the fit; with any of the new
     flags `last.ckpt` is also written every int(total steps * trainer.save_every_n_steps) steps, and `--resume`
-    continues from it (`--stop-after N` is the interruption)"""
+    continues from it (`--stop-after N` is the interruption).  `test_after_fit`: the default of `--test` (ae_s2's
+    `__main__` calls trainer.test after trainer.fit; `--no-test` leaves it out)"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default=os.path.join(here, "config.yaml"))
     ap.add_argument("--max-steps", type=int, default=-1)
@@ -198,7 +201,11 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
                          "when the config names sevir_lr and the store holds raw 384x384x49 events, else none")
     ap.add_argument("--validate", action="store_true",
                     help="run the validation pass on synthetic events too (with --data-dir it always runs)")
-    ap.add_argument("--test", action="store_true", help="run the test loop after the fit")
+    ap.add_argument("--test", action=argparse.BooleanOptionalAction, default=test_after_fit,
+                    help="run the test loop after the fit")
+    ap.add_argument("--matmul-precision", default="high", choices=["highest", "high", "medium"],
+                    help="reference: torch.set_float32_matmul_precision('high').  'medium' = bf16 operands with fp32 "
+                         "accumulation in the matrix-core kernels")
     ap.add_argument("--resume", action="store_true", help="continue from last.ckpt if there is one")
     ap.add_argument("--plots", default=None, metavar="DIR",
                     help="write target / prediction / difference panels of the steps that plot in the reference into "
@@ -212,6 +219,7 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
     cli = C.from_dotlist(unknown)
     helpers.check_yaml(cfg, cli)
     cfg = C.merge(cfg, cli)
+    ops.set_float32_matmul_precision(args.matmul_precision)
     rank, world, local = parallel.init_from_env()
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
@@ -367,7 +375,8 @@ def open_data(cfg, layout, path, data_dir, data_format="npy", presample="auto", 
         return mk(ev_train, True), mk(store(start_date=VAL_DATE, end_date=TEST_DATE), False), mk(ev_test, False), pooled[0], line
     dm = SEVIRLightningDataModule(ev_train, ev_test, dataset_name="sevirlr" if d.name == "sevir_lr" else d.name,
                                   num_workers=d.num_workers, batch_size=d.batch_size, seq_len=d.seq_len, stride=d.stride,
-                                  layout=layout, aug_mode=str(d.aug_mode), val_ratio=d.val_ratio, seed=d.seed,
+                                  layout=layout, aug_mode=str(d.get("aug_mode", "0")), val_ratio=d.get("val_ratio", 0.1),
+                                  seed=d.get("seed", 0),
                                   ret_contiguous=False, device=device, presample=factors)
     dm.prepare_data()
     dm.setup()

@@ -1908,6 +1908,22 @@ def aekl_posterior(moments, noise=None):
     return mean, logvar, std, sample
 
 
+def aekl_posterior_seq(moments, noise):
+    """moments (B*T, 2C, h, w) of the frames f = b*T + t, noise (T, B, C, h, w) -> z (B, T, C, h, w) = mean + std * noise:
+    the sample of aekl_posterior, bit for bit, without its other three outputs and without a permuted copy of the noise"""
+    _chk(moments, noise)
+    if moments.dim() != 4 or noise.dim() != 5 or moments.shape[1] % 2:
+        raise _lib.WfaeError(f"aekl_posterior_seq: expected moments (B*T, 2C, h, w) and noise (T, B, C, h, w), got "
+                             f"{tuple(moments.shape)} and {tuple(noise.shape)}")
+    t, b = noise.shape[:2]
+    n, c2, h, wd = moments.shape
+    if (t * b, c2 // 2, h, wd) != (n, *noise.shape[2:]):
+        raise _lib.WfaeError(f"aekl_posterior_seq: noise {tuple(noise.shape)} does not fit moments {tuple(moments.shape)}")
+    z = torch.empty((b, t, c2 // 2, h, wd), dtype=torch.float32, device=moments.device)
+    _call("wfae_aekl_posterior_seq", 0, 4 * moments.numel() * 2, _p(moments), _p(noise), _p(z), b, t, c2 // 2, h * wd, _stream())
+    return z
+
+
 # ---- AutoencoderKL backward (include/wfae.h "AutoencoderKL backward"; csrc/aekl_bwd.hip)
 def _aekl_out_plane(kind, h, wd):
     return (h, wd) if kind == 0 else ((h - 2) // 2 + 1, (wd - 2) // 2 + 1) if kind == 1 else (2 * h, 2 * wd)

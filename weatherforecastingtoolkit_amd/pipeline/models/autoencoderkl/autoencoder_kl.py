@@ -76,10 +76,16 @@ class AutoencoderKL(tnn.Module):
         if x.shape[2] % d or x.shape[3] % d:
             raise WfaeError(f"AutoencoderKL.encode: the plane {tuple(x.shape[2:])} is not divisible by {d}")
         with self._graph():
-            return DiagonalGaussianDistribution(conv1x1(self.quant_conv, self.encoder(x)))
+            return conv1x1(self.quant_conv, self.encoder(x))
+
+    def moments(self, x):
+        """the quant_conv output (N, 2 * latent channels, h, w) that `encode` wraps into the distribution"""
+        return self._encode(self._check("encode", x, self.encoder.conv_in.in_channels))
 
     def encode(self, x):
-        return self._encode(self._check("encode", x, self.encoder.conv_in.in_channels))
+        moments = self.moments(x)
+        with self._graph():
+            return DiagonalGaussianDistribution(moments)
 
     def _decode(self, z):
         with self._graph():
