@@ -584,7 +584,7 @@ __global__ void clip_coef_kernel(const double* __restrict__ parts, int n, float 
     for (int i = 0; i < n; ++i) s += parts[i];
     const float total = (float)sqrt(s) * pre_scale;
     const float coef = max_norm / (total + 1e-6f);
-    out[0] = coef < 1.f ? coef : 1.f;
+    out[0] = coef > 1.f ? 1.f : coef;   // torch.clamp(max=1): a NaN norm stays NaN and reaches every gradient
     out[1] = total;
   }
 }
@@ -596,7 +596,8 @@ __global__ void adaptive_weight_kernel(const double* __restrict__ ss_rec, const 
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     const float nr = (float)sqrt(ss_rec[0]), nd = (float)sqrt(ss_disc[0]);
     float w = disc_weight * (nr / (nd + 1e-4f));
-    w = fminf(fmaxf(w, 0.f), 1e4f);
+    w = w < 0.f ? 0.f : w;        // torch.clamp keeps a NaN, fmaxf / fminf would drop it
+    w = w > 1e4f ? 1e4f : w;
     out[0] = w;
   }
 }

@@ -79,7 +79,13 @@ class FusedAdamW(torch.optim.Optimizer):
 
     exact_complements=True forms 1 - beta1 and 1 - beta2 in double and rounds once, as torch does (wfae_adamw_c).  The
     default keeps the fp32 complements of the rounded betas (1.f - 0.999f is 1.3e-5 short of 0.001, every step 6.4e-6
-    larger than torch's — visible only on parameters that start at zero), so existing runs reproduce."""
+    larger than torch's — visible only on parameters that start at zero), so existing runs reproduce.
+
+    One difference from torch is deliberate: the step count, and with it the bias corrections 1 - beta^t, belongs to the
+    parameter GROUP, where torch keeps one per parameter.  A parameter that receives its first gradient at group step 3 is
+    corrected with t = 3 here and with t = 1 in torch.  A per-parameter t would need one launch per parameter; the
+    single launch over the arena is the point of this class.  Parameters whose gradients are present from the first
+    step, or absent throughout (they are skipped: no decay, no moments), step exactly as in torch."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, flatten=True,
                  exact_complements=False):
