@@ -1146,6 +1146,30 @@ int wfae_panel_render(const float* pred, const float* target, const uint8_t* lut
 size_t wfae_range_count_workspace_bytes(int64_t n);
 int wfae_range_count(const float* x, int64_t n, int64_t* count, void* ws, size_t ws_bytes, wfae_stream_t stream);
 
+/* ---- latent cache of the frozen AutoencoderKL provider (csrc/latent_cache.hip; experiments/v1_experiments/_latents.py
+ * `LatentCache`).  Added within ABI version 103; nothing changed.
+ * A row is one frame's payload of L fp32 values: the posterior mode (L = C h w) or the moments (L = 2 C h w).  table:
+ * (capacity, L).  slots and index are device int32.
+ * latent_scatter: for m < M with 0 <= slots[m] < capacity, table[slots[m], :] = src[m, :]; slots[m] == -1 skips row m and
+ *   leaves the table untouched.  Distinct rows never share a slot (the caller's contract: the rows are written without
+ *   atomics).  Any other slot value is the caller's error, to be checked on the host copy the slots were built from; the
+ *   kernel skips such a row rather than follow it.
+ * latent_gather: output frame f = b * T + t reads row table[index[f]] if index[f] >= 0, else fresh[-1 - index[f]]
+ *   (fresh: (M, L), the rows encoded this step; may be NULL with M = 0 when no index is negative).
+ *   mode 0: out (B * T, L), out[f, :] = row.
+ *   mode 1: the row holds moments, L = 2 CHW, noise (T, B, CHW) draw-major, out (B * T, CHW):
+ *     out[f, r] = fmaf(expf(0.5f * clamp(row[CHW + r], -30, 20)), noise[(t * B + b) * CHW + r], row[r]),
+ *     the expression and operand order of wfae_aekl_posterior_seq: its bits for the same moments.
+ *   An index outside [-M, capacity) is the caller's error (host copy, as above); the kernel leaves such a frame unwritten.
+ * Both: grid-stride streaming copies, 16-byte accesses when L % 4 == 0 (mode 1: CHW % 4 == 0) and every pointer is 16-byte
+ *   aligned, scalar otherwise.  No atomics: two launches give the same bits.
+ * Errors, all before any launch: null pointers (noise in mode 1; fresh with M > 0) and noise given in mode 0
+ *   WFAE_ERR_NULL_POINTER; a size < 1, M < 0 (gather), a mode other than 0 or 1, mode 1 with odd L, or an array of 2^39
+ *   elements WFAE_ERR_BAD_SHAPE. */
+int wfae_latent_scatter(const float* src, const int* slots, float* table, int M, int L, int capacity, wfae_stream_t stream);
+int wfae_latent_gather(const float* table, const float* fresh, const int* index, const float* noise, float* out, int B, int T,
+                       int L, int mode, int capacity, int M, wfae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

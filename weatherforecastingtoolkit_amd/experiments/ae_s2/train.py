@@ -63,6 +63,8 @@ class Model(_dlinear.Model):
         if batch.dim() != 5 or batch.shape[2] != 1:
             raise WfaeError(f"expected frames (B, T, 1, H, W), got {tuple(batch.shape)}; latents go to train_latents / "
                             "validate_latents")
+        if self.batch_ids is not None:
+            return batch, self.autoencoder.encode(batch.contiguous(), generator=self.generator, ids=self.batch_ids)
         return batch, self.autoencoder.encode(batch.contiguous(), generator=self.generator)
 
 

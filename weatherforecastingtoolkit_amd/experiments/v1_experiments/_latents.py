@@ -5,12 +5,96 @@ re-export it under the name `Autoencoder`.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as tnn
 
 from ... import ops
 from ..._lib import WfaeError
 from ...pipeline.models.ae_64x8x8_lin import PosAwareAE_TF
+
+
+class LatentCache:
+    """Latents of a frozen provider, kept on the device so that a frame is encoded once: a table (capacity, L) fp32 of one
+    row per frame — the posterior mode (L = C h w), or the moments (L = 2 C h w) of a sampling provider, whose noise is
+    applied after the table is read — and a host dict key -> slot, a key being (split, frame id).  No eviction: slots are
+    handed out in first-seen order until `capacity`; a frame met after that is encoded every time it appears.  The table
+    is allocated at the first `rows()`, when L is known.
+    `pass_frames[split]`: the number of frames per encoder pass that the split's cached rows were computed with (see
+    `Autoencoder._encode_cached`: the encoder's GEMM routes depend on it, so it is part of what a row is).
+    Counters: `misses` frames that were encoded, `hits` frames that were asked for and not encoded (read from the table,
+    or a repeat inside one batch of a frame encoded in that step: `hits` is not the number of table reads), `bypassed`
+    frames of batches that went around the cache, `frames_cached` slots in use, `bytes` of the table."""
+
+    def __init__(self, capacity):
+        self.capacity = int(capacity)
+        if self.capacity < 1:
+            raise ValueError(f"LatentCache: capacity {capacity}, expected at least one frame")
+        self.slot, self.table, self.latent_shape, self.pass_frames = {}, None, None, {}
+        self.hits = self.misses = self.bypassed = 0
+
+    @property
+    def frames_cached(self):
+        return len(self.slot)
+
+    @property
+    def bytes(self):
+        return 0 if self.table is None else self.table.numel() * 4
+
+    def stats(self):
+        return {"hits": self.hits, "misses": self.misses, "frames_cached": self.frames_cached, "capacity": self.capacity,
+                "MiB": round(self.bytes / 2 ** 20, 3), "bypassed": self.bypassed}
+
+    def plan(self, keys):
+        """host only.  keys: the B*T frames of a batch in (b, t) order -> (missing, slots, index):
+        missing: the keys to encode, unique, in first-seen order (a frame that appears twice is encoded once);
+        slots: int64, one per missing key: the table row it gets (and keeps), -1 once the table is full;
+        index: int64, one per frame: the table row (>= 0) of a frame cached by an earlier batch, else -1 - j for row j of
+        this batch's encoded frames — also for those that get a slot now: they are read from `fresh`, not from the table"""
+        missing, slots, index, fresh = [], [], [], {}
+        for k in keys:
+            if k in fresh:
+                index.append(-1 - fresh[k])
+                continue
+            s = self.slot.get(k)
+            if s is not None:
+                index.append(s)
+                continue
+            j = fresh[k] = len(missing)
+            missing.append(k)
+            if len(self.slot) < self.capacity:
+                slots.append(len(self.slot))
+                self.slot[k] = slots[-1]
+            else:
+                slots.append(-1)
+            index.append(-1 - j)
+        self.misses += len(missing)
+        self.hits += len(index) - len(missing)
+        return missing, np.asarray(slots, dtype=np.int64), np.asarray(index, dtype=np.int64)
+
+    def rows(self, latent_shape, device):
+        """the table for rows of `latent_shape` (C or 2C, h, w), allocated at the first call"""
+        if self.table is None:
+            self.latent_shape = tuple(int(v) for v in latent_shape)
+            self.table = torch.empty((self.capacity, int(np.prod(self.latent_shape))), dtype=torch.float32, device=device)
+        elif tuple(latent_shape) != self.latent_shape:
+            raise WfaeError(f"LatentCache: rows of shape {tuple(latent_shape)}, the table holds {self.latent_shape}")
+        return self.table
+
+    def clear(self):
+        """forget every frame (the table stays allocated and is refilled)"""
+        self.slot.clear()
+
+    def serves(self, split, n, chunk_frames):
+        """host only.  Whether a batch of n frames of `split` goes through the cache, given that the uncached encode runs
+        it in passes of `chunk_frames` frames (0: one pass of n) -> the pass size, or 0 for "go around the cache".
+        A batch is served when all its uncached passes have one size and that size is the split's (set by its first
+        served batch): a short last batch, or one with a smaller tail chunk, is not"""
+        size = chunk_frames if chunk_frames > 0 else n
+        if n % size or self.pass_frames.setdefault(split, size) != size:
+            self.bypassed += n
+            return 0
+        return size
 
 
 class Autoencoder(tnn.Module):
@@ -40,6 +124,7 @@ class Autoencoder(tnn.Module):
         self.kind = kind
         self.chunk_frames = 0
         self.sample = False
+        self.cache = None
         if kind == "autoencoder_kl":
             self.autoencoder = self._build_autoencoder_kl(cfg or {})
             chunk = (cfg or {}).get("chunk_frames")
@@ -107,14 +192,86 @@ class Autoencoder(tnn.Module):
             torch.randn((b, *latent_shape), generator=generator, device=device, dtype=torch.float32, out=noise[i])
         return noise
 
+    def enable_cache(self, capacity_frames):
+        """keep the latents of up to `capacity_frames` frames on the device (`LatentCache`); `encode(x, ids=...)` then
+        encodes a frame once.  -> the cache"""
+        if self.kind != "autoencoder_kl":
+            raise WfaeError(f"Autoencoder.enable_cache: kind {self.kind!r} is not cached, only autoencoder_kl is.  The other "
+                            "kinds' kernel routes are chosen from the batch size (ae_gan.convautoencoder: the K-split of its "
+                            "small route depends on the total column count; for the rest this is a precaution), so a "
+                            "cached latent would not be the bits of the uncached encode; for the AutoencoderKL encoder the "
+                            "cache keeps the number of frames per pass that the uncached encode uses")
+        self.cache = LatentCache(capacity_frames)
+        return self.cache
+
+    def _encode_cached(self, x, ids, generator, noise):
+        """`encode` through the cache: plan, encode the missing frames, scatter them, one gather launch; None for a
+        batch that goes around the cache.
+        A frame's latent depends on how many frames share its encoder pass: the mid-block attention's projections are
+        GEMMs of frames x tokens rows, and their K-split and tile size are chosen from the row count (gemm.hip
+        `pick_splits`), i.e. their summation order is.  It does not depend on which frames those are, nor on the frame's
+        place in the pass: convolutions, GroupNorm and attention work per sample, a GEMM row's sums per row.  So the
+        missing frames are encoded in passes of exactly the size the uncached encode uses, filled up with repeats of the
+        last missing frame whose results are dropped; one missing frame costs one whole pass.  A batch whose uncached
+        passes are not all of that size (`LatentCache.serves`) is encoded as without the cache and neither read from
+        nor written to the table"""
+        b, t, c, h, w = x.shape
+        split, fid = ids
+        fid = np.asarray(fid).reshape(-1)
+        if fid.size != b * t:
+            raise WfaeError(f"Autoencoder.encode: {fid.size} frame ids for a batch of {b} x {t} frames")
+        cache = self.cache
+        size = cache.serves(split, b * t, self.chunk_frames)
+        if not size:
+            return None
+        keys = [(split, int(i)) for i in fid]
+        missing, slots, index = cache.plan(keys)
+        fresh = None
+        if missing:
+            try:
+                first = {}
+                for f, k in enumerate(keys):
+                    first.setdefault(k, f)
+                rows = [first[k] for k in missing]
+                rows += [rows[-1]] * (-len(rows) % size)          # whole passes of `size` frames
+                frames = x.reshape(b * t, c, h, w)
+                if rows != list(range(b * t)):
+                    frames = frames[torch.as_tensor(rows, device=x.device)]
+                ae = self.autoencoder
+                fresh = torch.cat([ae.moments(f) if self.sample else ae.encode(f).mode()
+                                   for f in (frames[i:i + size].contiguous() for i in range(0, len(rows), size))])
+                table = cache.rows(fresh.shape[1:], fresh.device)
+                fresh = fresh[:len(missing)].reshape(len(missing), -1)
+                if (slots >= 0).any():
+                    ops.latent_scatter(fresh, slots, table)
+            except BaseException:
+                cache.clear()       # the plan handed out slots for rows that may not have been written
+                raise
+        table, shape = cache.table, cache.latent_shape
+        if self.sample:
+            shape = (shape[0] // 2, *shape[1:])
+            if noise is None:
+                noise = self.draw_noise(b, t, shape, table.device, generator)
+            elif tuple(noise.shape) != (t, b, *shape):
+                raise WfaeError(f"Autoencoder.encode: noise {tuple(noise.shape)}, expected {(t, b, *shape)}")
+            noise = noise.contiguous()
+        return ops.latent_gather(table, fresh, index, (b, t), noise).view(b, t, *shape)
+
     @torch.no_grad()
-    def encode(self, x, generator=None, noise=None):
+    def encode(self, x, generator=None, noise=None, ids=None):
         """x (B, T, 1, H, W) -> (B, T, C, h, w).  `generator` / `noise` (T, B, C, h, w) belong to `sample: true`: `noise`
-        replaces the draw"""
+        replaces the draw.  `ids` = (split, the B*T int64 frame ids in (b, t) order) names the frames for the cache of
+        `enable_cache`: the result is the same bits, frames met before are not encoded again (a batch whose encoder
+        passes are not of the cached size goes around the cache).  Without a cache `ids` is not read, and without `ids`
+        the cache is not used"""
         b, t, c, h, w = x.shape
         frames = x.reshape(b * t, c, h, w)
         if not self.sample and (generator is not None or noise is not None):
             raise WfaeError("Autoencoder.encode: generator / noise need the sampled provider (autoencoder_kl with sample: true)")
+        if self.cache is not None and ids is not None:
+            z = self._encode_cached(x, ids, generator, noise)
+            if z is not None:
+                return z
         if self.kind == "autoencoder_kl" and self.sample:
             moments = torch.cat([self.autoencoder.moments(f) for f in self._chunks(frames)])
             shape = (moments.shape[1] // 2, *moments.shape[2:])

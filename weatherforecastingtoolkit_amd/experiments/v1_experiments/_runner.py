@@ -36,6 +36,7 @@ class Step:
     trained = "predictor"        # the attribute that holds the trained sub-module
     panels = None                # helpers.PanelSink with `--plots DIR` on rank 0: the steps that plot draw into it
     exact_complements = False    # see optim.FusedAdamW
+    batch_ids = None             # with `--latent-cache`: (split, frame ids) of the loader batch the driver hands to a step
 
     def configure_optimizers(self):
         o, sp = self.cfg.optim, self.cfg.cosine_warmup
@@ -74,6 +75,8 @@ class Step:
                 raise WfaeError("a batch of frames (B, T, H, W) needs the frozen autoencoder; pass latents "
                                 "(B, T, C, h, w) or construct Model(cfg, autoencoder=...)")
             frames = batch.unsqueeze(2)
+            if self.batch_ids is not None:
+                return frames, self.autoencoder.encode(frames, ids=self.batch_ids)
             return frames, self.autoencoder.encode(frames)
         return None, batch
 
@@ -188,7 +191,10 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
     pass follows every training epoch and the last step; `--test` adds a test pass after the fit; with any of the new
     flags `last.ckpt` is also written every int(total steps * trainer.save_every_n_steps) steps, and `--resume`
     continues from it (`--stop-after N` is the interruption).  `test_after_fit`: the default of `--test` (ae_s2's
-    `__main__` calls trainer.test after trainer.fit; `--no-test` leaves it out)"""
+    `__main__` calls trainer.test after trainer.fit; `--no-test` leaves it out).  `--latent-cache FRAMES` keeps the frozen
+    AutoencoderKL's latents on the device (`enable_latent_cache`): the training, validation and test-after-fit steps get
+    their batch's frame ids in `model.batch_ids`, and one `latent_cache` line is printed in front of `done`; with
+    `--mode test` the flag is refused"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default=os.path.join(here, "config.yaml"))
     ap.add_argument("--max-steps", type=int, default=-1)
@@ -210,11 +216,20 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
     ap.add_argument("--plots", default=None, metavar="DIR",
                     help="write target / prediction / difference panels of the steps that plot in the reference into "
                          "DIR as PNG files, with one line per figure in DIR/index.jsonl (rank 0)")
+    ap.add_argument("--latent-cache", type=int, default=0, metavar="FRAMES",
+                    help="keep the frozen AutoencoderKL's latents of up to FRAMES frames on the device, so that a frame is "
+                         "encoded once per run and not once per epoch (each rank caches its own shard; a resumed run "
+                         "refills it).  The run's numbers are bit for bit those without the flag: missing frames are "
+                         "encoded in passes of the size the uncached encode uses, and a batch of another pass size (a "
+                         "short last batch) goes around the cache.  Fit only.  0 = off")
     ap.add_argument("--stop-after", type=int, default=-1,
                     help="stop (and checkpoint) after this many optimiser steps without changing the schedule: an "
                          "interrupted run that --resume continues")
     args, unknown = ap.parse_known_args(argv)
     mode = getattr(args, "mode", "fit")
+    if args.latent_cache and mode == "test":        # before the device is opened
+        raise WfaeError("--latent-cache with --mode test: a test run is a single pass over the loader, no frame is met twice; "
+                        "the flag belongs to a fit (its validation and test-after-fit passes included)")
     cfg = C.load(args.config)
     cli = C.from_dotlist(unknown)
     helpers.check_yaml(cfg, cli)
@@ -238,6 +253,7 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
     model = build(cfg, size).to(dev).train()
     if getattr(model, "autoencoder", None) is not None:
         model.autoencoder.eval()
+    cache = enable_latent_cache(model, loader, args.latent_cache) if args.latent_cache else None
     # the figures' sink: rank 0's, and only with --plots; a model's steps draw nothing while `panels` is None
     model.panels = helpers.make_sink(args.plots, rank, cfg.trainer, total, len(loader) if mode == "test" else len(val),
                                      len(loader) if mode == "test" else len(test))
@@ -284,7 +300,8 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
                 break
             if model.panels is not None:
                 model.panels.global_step, model.panels.epoch, model.panels.batch_idx = step, step // nb, i
-            loss, gn = model.training_step(_frames(loader[i]))
+            with batch_ids(model, loader, i, "train", cache):
+                loss, gn = model.training_step(_frames(loader[i]))
             step += 1
             if rank == 0 and step % max(1, cfg.trainer.log_every_n_steps) == 0:
                 print(json.dumps({"step": step, "train_loss": float(loss), "grad_norm": float(gn),
@@ -304,8 +321,45 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
     if args.test:
         report(evaluate(model, test, "test", cfg.trainer.limit_test_batches, world, step, nb), rank)
     if rank == 0:
+        if cache is not None:
+            print(json.dumps({"latent_cache": cache.stats()}), flush=True)
         print("done")
     return 0
+
+
+def enable_latent_cache(model, loader, frames):
+    """`--latent-cache FRAMES`: the cache of the model's frozen provider, or the reason the run cannot have one"""
+    if frames < 0:
+        raise WfaeError(f"--latent-cache {frames}: a count of frames, 0 = off")
+    ae = getattr(model, "autoencoder", None)
+    if not isinstance(ae, Autoencoder):
+        raise WfaeError(f"--latent-cache: {type(model).__module__}.Model has no frozen latent provider (_latents.Autoencoder) "
+                        "whose latents could be kept: it trains on frames or on its own encoder")
+    if not isinstance(model, Step):
+        raise WfaeError(f"--latent-cache: {type(model).__module__}.Model does not take the driver's frame ids")
+    cache = ae.enable_cache(frames)                 # refuses every kind but autoencoder_kl
+    aug = str(getattr(getattr(loader, "loader", loader), "aug_mode", "0"))
+    if aug != "0":
+        ae.cache = None
+        raise WfaeError(f"--latent-cache: the training loader augments (dataset.aug_mode {aug!r}), so a frame differs from "
+                        "epoch to epoch and its latent cannot be kept; the flag needs aug_mode \"0\"")
+    return cache
+
+
+class batch_ids:
+    """around a step on `loader[i]`: `model.batch_ids` = (split, the batch's frame ids in (b, t) order), None again
+    afterwards.  Without a cache it does nothing"""
+
+    def __init__(self, model, loader, i, split, cache):
+        self.model, self.ids = model, None if cache is None else (split, loader.frame_ids(i).reshape(-1))
+
+    def __enter__(self):
+        if self.ids is not None:
+            self.model.batch_ids = self.ids
+
+    def __exit__(self, *exc):
+        if self.ids is not None:
+            self.model.batch_ids = None
 
 
 def _frames(batch):
@@ -340,6 +394,11 @@ class RankShard:
 
     def set_epoch(self, epoch):
         self.loader.set_epoch(epoch)
+
+    def frame_ids(self, i):
+        if i >= len(self):
+            raise IndexError(i)
+        return self.loader.frame_ids(i * self.world + self.rank)
 
 
 def open_data(cfg, layout, path, data_dir, data_format="npy", presample="auto", *, device=None, rank=0, world=1,
@@ -428,7 +487,8 @@ def evaluate(model, loader, split, limit, world, step=None, nb_train=1):
     rows = []
     with torch.random.fork_rng(devices=[torch.cuda.current_device()] if torch.cuda.is_available() else []):
         for i in range(n):
-            res = getattr(model, name)(_frames(loader[i]), i)
+            with batch_ids(model, loader, i, split, getattr(getattr(model, "autoencoder", None), "cache", None)):
+                res = getattr(model, name)(_frames(loader[i]), i)
             rows.append(res[1] if isinstance(res, tuple) else {f"{split}_loss": res})
     Fn._seed_counter[0] = counter
     for m, training in modes:

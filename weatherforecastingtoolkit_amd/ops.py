@@ -10,6 +10,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1922,6 +1923,74 @@ def aekl_posterior_seq(moments, noise):
     z = torch.empty((b, t, c2 // 2, h, wd), dtype=torch.float32, device=moments.device)
     _call("wfae_aekl_posterior_seq", 0, 4 * moments.numel() * 2, _p(moments), _p(noise), _p(z), b, t, c2 // 2, h * wd, _stream())
     return z
+
+
+# ---- latent cache (include/wfae.h "latent cache"; csrc/latent_cache.hip)
+def _host_i32(name, what, v, lo, hi, device):
+    """a HOST list / array / tensor of integers in [lo, hi) -> (the int64 numpy copy that was checked, the int32 device
+    tensor built from it).  The kernels trust these values, so they are checked here, where they were made.  The copy goes
+    through pinned memory and does not block: a pageable one would make the host wait for the stream, and with it for the
+    encoder launches queued in front"""
+    if isinstance(v, torch.Tensor):
+        if v.is_cuda:
+            raise _lib.WfaeError(f"{name}: {what} is checked on the host, pass the host copy (a list, an array or a CPU tensor)")
+        v = v.numpy()
+    a = np.asarray(v)
+    if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iu":
+        raise _lib.WfaeError(f"{name}: {what} must be a non-empty 1-D integer array, got shape {a.shape} of {a.dtype}")
+    a = a.astype(np.int64)
+    if int(a.min()) < lo or int(a.max()) >= hi:
+        raise _lib.WfaeError(f"{name}: {what} in [{int(a.min())}, {int(a.max())}], outside [{lo}, {hi})")
+    return a, torch.from_numpy(a.astype(np.int32)).pin_memory().to(device, non_blocking=True)
+
+
+def latent_scatter(src, slots, table):
+    """table[slots[m], :] = src[m, :] for the rows with slots[m] >= 0; slots[m] == -1 skips row m.  src (M, L), table
+    (capacity, L) fp32 on the device; `slots`: M host integers in [-1, capacity), no slot twice (rows are written without
+    atomics).  Writes into `table`, returns it"""
+    _chk(src, table)
+    if src.dim() != 2 or table.dim() != 2 or src.shape[1] != table.shape[1] or src.device != table.device:
+        raise _lib.WfaeError(f"latent_scatter: expected src (M, L) and table (capacity, L) on one device, got "
+                             f"{tuple(src.shape)} and {tuple(table.shape)}")
+    m, l = src.shape
+    cap = table.shape[0]
+    host, dev = _host_i32("latent_scatter", "slots", slots, -1, cap, src.device)
+    if host.size != m:
+        raise _lib.WfaeError(f"latent_scatter: {host.size} slots for {m} rows")
+    used = host[host >= 0]
+    if np.unique(used).size != used.size:
+        raise _lib.WfaeError("latent_scatter: two rows share a slot")
+    _call("wfae_latent_scatter", 0, 8 * used.size * l, _p(src), dev.data_ptr(), _p(table), m, l, cap, _stream())
+    return table
+
+
+def latent_gather(table, fresh, index, shape_bt, noise=None):
+    """output frame f = b*T + t reads table[index[f]] if index[f] >= 0, else fresh[-1 - index[f]].  table (capacity, L),
+    fresh (M, L) or None (no negative index), `index`: B*T host integers in [-M, capacity), shape_bt = (B, T).
+    noise None -> (B, T, L), a copy of the rows.  noise (T, B, C, h, w) with L = 2 C h w: the rows are moments and the result
+    is (B, T, C h w) = mean + std * noise, the bits of aekl_posterior_seq on the same moments"""
+    _chk(table, fresh, noise)
+    b, t = (int(v) for v in shape_bt)
+    if table.dim() != 2 or (fresh is not None and (fresh.dim() != 2 or fresh.shape[1] != table.shape[1] or fresh.shape[0] < 1
+                                                   or fresh.device != table.device)):
+        raise _lib.WfaeError(f"latent_gather: expected table (capacity, L) and fresh (M, L) on one device, got "
+                             f"{tuple(table.shape)} and {None if fresh is None else tuple(fresh.shape)}")
+    cap, l = table.shape
+    m = 0 if fresh is None else fresh.shape[0]
+    if b < 1 or t < 1:
+        raise _lib.WfaeError(f"latent_gather: shape_bt {(b, t)}")
+    host, dev = _host_i32("latent_gather", "index", index, -m, cap, table.device)
+    if host.size != b * t:
+        raise _lib.WfaeError(f"latent_gather: {host.size} indices for {b} x {t} frames")
+    lout = l
+    if noise is not None:
+        lout = l // 2
+        if l % 2 or noise.dim() < 3 or tuple(noise.shape[:2]) != (t, b) or noise.numel() != t * b * lout or noise.device != table.device:
+            raise _lib.WfaeError(f"latent_gather: noise {tuple(noise.shape)} does not fit {(t, b)} draws of rows of {l} moments")
+    out = torch.empty((b, t, lout), dtype=torch.float32, device=table.device)
+    _call("wfae_latent_gather", 0, 4 * b * t * (l + lout + (lout if noise is not None else 0)), _p(table), _p(fresh),
+          dev.data_ptr(), _p(noise), _p(out), b, t, l, 0 if noise is None else 1, cap, m, _stream())
+    return out
 
 
 # ---- AutoencoderKL backward (include/wfae.h "AutoencoderKL backward"; csrc/aekl_bwd.hip)

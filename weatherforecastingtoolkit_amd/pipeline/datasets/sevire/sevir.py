@@ -246,6 +246,14 @@ class SEVIRFrameLoader:
         n = self.num_seq_per_event
         return [e * n + s for e, s in self.sample_indices(index * self.num_shard + self.rank)]
 
+    def frame_ids(self, index):
+        """int64 (B, seq_len): the frame (event * raw_seq_len + its position in the event; the pooled frames with
+        presample) behind every frame of this rank's batch `index`.  Two batch frames with one id are the same pixels
+        as long as aug_mode is "0": what a cache of per-frame results keys on"""
+        idx = self.sample_indices(index * self.num_shard + self.rank)
+        first = np.asarray([e * self.raw_seq_len + s * self.stride for e, s in idx], dtype=np.int64)
+        return first[:, None] + np.arange(self.seq_len, dtype=np.int64)[None, :]
+
     def batch_augment_params(self, index, epoch=None):
         """[(hflip, vflip, angle)] of this rank's batch `index`"""
         epoch = self.epoch if epoch is None else epoch
