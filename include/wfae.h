@@ -1170,6 +1170,25 @@ int wfae_latent_scatter(const float* src, const int* slots, float* table, int M,
 int wfae_latent_gather(const float* table, const float* fresh, const int* index, const float* noise, float* out, int B, int T,
                        int L, int mode, int capacity, int M, wfae_stream_t stream);
 
+/* ---- row-invariant nn.Linear forward (csrc/linear_rowinv.hip): the attention projections of the frozen AutoencoderKL in
+ * pass-invariant mode (`AutoencoderKL.pass_invariant()`, functional.aekl_attention(row_invariant=True)), and its 1x1
+ * convolutions on tokens (functional.aekl_conv1x1_rowinv).  Added within ABI
+ * version 103; nothing changed: 230 entry points.
+ * y[b,o] = sum_i x[b,i] w[o,i] + bias[o], x (B, In), w (Out, In), bias (Out) or NULL, y (B, Out), fp32, no workspace.
+ * Contract: the bits of y[b,o] are a function of x[b,:], w[o,:], bias[o], In, Out and the matmul precision only — not of B,
+ *   of the row's index, of which other rows are in the call, nor of whether the pointers allow 16-byte loads.  (wfae_linear_fwd
+ *   chooses its row tile, its K-split — the summation order — and at fp32 precision its instruction from B and from the
+ *   workspace size.)  The tile (64 x 64 x 16) and the k-loop follow from (In, Out) alone, K is never split across
+ *   workgroups, every output element is one accumulator chain over ascending k with the bias added last, rows and columns
+ *   past the edge are masked.  WFAE_PRECISION_FP32: v_mfma_f32_32x32x2_f32, a k-ordered fp32 fmaf chain, whatever
+ *   wfae_set_split_gemm says; WFAE_PRECISION_BF16: operands rounded to bf16 (nearest even), v_mfma_f32_32x32x16_bf16,
+ *   fp32 accumulation.
+ * Served: B >= 1; In and Out multiples of 32 up to 4096.
+ * Errors, all before any launch: x, w or y NULL WFAE_ERR_NULL_POINTER; a size < 1 WFAE_ERR_BAD_SHAPE; any other In or Out
+ *   WFAE_ERR_UNSUPPORTED. */
+int wfae_linear_fwd_rowinv(const float* x, const float* w, const float* bias, float* y, int B, int In, int Out,
+                           wfae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,10 @@ device events, one untimed step of each first:
 The line holds the median of each, every round's triple, (b) - (a) next to the spread (min .. max) of the (a) rounds, the
 misses and hits counted in the (b) and (c) windows, whether the cached latents are the uncached bits at this geometry (all
 miss, all hit, and partial misses: the cached batch with its last 1, 5 and 13 frames replaced by unseen ones), the
-table's size, and the gather kernel on its own: the call a step makes (B*T frames; launch-bound at this size) and one over
+table's size, the same three variants with the provider in pass-invariant mode (`--invariant-encode`; both modes alternate
+inside every round, its uncached step is held against the default uncached step of the same run and the spread of both),
+a step with 1, 5 and 13 of the batch's frames missing in both modes (`partial_miss_step_ms`: the default mode encodes whole
+passes for them, the pass-invariant mode the missing frames), and the gather kernel on its own: the call a step makes (B*T frames; launch-bound at this size) and one over
 the whole table, whose bytes (row + noise read, latent written) over device time is the figure to hold against the
 6.1 - 6.2 TB/s of the project's other streaming kernels.  There are no thresholds: the tool measures.
 """
@@ -91,11 +94,40 @@ def gather_alone(table, latent_shape, sample, bt, calls, dev):
             "ops_call_ms": round(call_ms, 4)}
 
 
+def bits_check(ae, cache, x, ids, n, bt, dev):
+    """the cached latents against the uncached ones of the provider's present mode, on one noise where the provider samples:
+    all miss, all hit, and partial misses — the cached batch with its last 1, 5 and 13 frames replaced by unseen ones (other
+    pixels, new ids); a partial miss counts as equal only if exactly k frames were counted as missed"""
+    with torch.no_grad():
+        plain = ae.encode(x)
+        shape = tuple(plain.shape[2:])
+        noise = ae.draw_noise(bt[0], bt[1], shape, dev) if ae.sample else None
+        plain = ae.encode(x, noise=noise)
+        cache.clear()
+        missed = ae.encode(x, noise=noise, ids=ids)
+        hit = ae.encode(x, noise=noise, ids=ids)
+        partial = {}
+        for k in (1, 5, 13):
+            if k >= n:
+                continue
+            flat = x.reshape(n, *x.shape[2:]).clone()
+            flat[n - k:] = 1.0 - flat[n - k:]
+            x2 = flat.view_as(x)
+            ids2 = ids[1].copy()
+            ids2[n - k:] = n + 100 * k + np.arange(k)
+            m0 = cache.misses
+            got = ae.encode(x2, noise=noise, ids=("train", ids2))
+            partial[str(k)] = bool(torch.equal(got, ae.encode(x2, noise=noise))) and cache.misses - m0 == k
+    return {"miss": bool(torch.equal(plain, missed)), "hit": bool(torch.equal(plain, hit)), "partial_miss_of_k_frames": partial}
+
+
 def measure(name, model, frames, bt, prec, a, dev):
     ae = model.autoencoder
     cache = ae.enable_cache(a.capacity)
     n = bt[0] * bt[1]
     ids = ("train", np.arange(n, dtype=np.int64))
+    ks = [k for k in (1, 5, 13) if k < n]
+    unseen = [1 << 20]              # ids of the frames a partial-miss step has not met: a new one for every missing frame
 
     def uncached():
         model.batch_ids = None
@@ -110,57 +142,75 @@ def measure(name, model, frames, bt, prec, a, dev):
         model.batch_ids = ids
         model.training_step(frames)
 
-    for fn in (uncached, all_miss, all_hit):
-        timed(fn, 1)
-    rounds, counts = [], {"all_miss": [0, 0], "all_hit": [0, 0]}
-    for _ in range(a.rounds):
-        row = []
-        for fn in (uncached, all_miss, all_hit):
-            h, m = cache.hits, cache.misses
-            row.append(timed(fn, a.steps))
-            if fn is not uncached:
-                counts[fn.__name__][0] += cache.misses - m
-                counts[fn.__name__][1] += cache.hits - h
-        rounds.append(row)
-    model.batch_ids = None
-    ta, tb, tc = (statistics.median(r[i] for r in rounds) for i in range(3))
-    a_runs = [r[0] for r in rounds]
-
-    # the cached latents against the uncached ones at this geometry and precision, on one noise where the provider samples
-    x = frames if frames.dim() == 5 else frames.unsqueeze(2)
-    with torch.no_grad():
-        shape = cache.latent_shape
-        noise = ae.draw_noise(bt[0], bt[1], (shape[0] // 2, *shape[1:]), dev) if ae.sample else None
-        plain = ae.encode(x, noise=noise)
-        cache.clear()
-        missed = ae.encode(x, noise=noise, ids=ids)
-        hit = ae.encode(x, noise=noise, ids=ids)
-        # partial misses: the cached batch with its last k frames replaced by unseen ones (other pixels, new ids)
-        partial = {}
-        for k in (1, 5, 13):
-            if k >= n:
-                continue
-            flat = x.reshape(n, *x.shape[2:]).clone()
-            flat[n - k:] = 1.0 - flat[n - k:]
-            x2 = flat.view_as(x)
+    def partial(k):
+        def step():                 # the batch that hits, its last k frames under ids the table has not seen
             ids2 = ids[1].copy()
-            ids2[n - k:] = n + 100 * k + np.arange(k)
-            m0 = cache.misses
-            got = ae.encode(x2, noise=noise, ids=("train", ids2))
-            partial[str(k)] = bool(torch.equal(got, ae.encode(x2, noise=noise))) and cache.misses - m0 == k
+            ids2[n - k:] = unseen[0] + np.arange(k)
+            unseen[0] += k
+            model.batch_ids = ("train", ids2)
+            model.training_step(frames)
+        step.__name__ = f"partial_{k}"
+        return step
+
+    # one mode after the other inside every round; all_miss refills the table that the change of mode emptied, all_hit and
+    # the partial misses follow it
+    variants = [uncached, all_miss, all_hit, *(partial(k) for k in ks)]
+    modes = ("default", "pass_invariant")
+    for mode in modes:
+        ae.set_pass_invariant(mode == "pass_invariant")
+        for fn in variants:
+            timed(fn, 1)
+    rounds = {mode: [] for mode in modes}
+    counts = {mode: {fn.__name__: [0, 0] for fn in variants[1:]} for mode in modes}
+    for _ in range(a.rounds):
+        for mode in modes:
+            ae.set_pass_invariant(mode == "pass_invariant")
+            row = []
+            for fn in variants:
+                h, m = cache.hits, cache.misses
+                row.append(timed(fn, a.steps))
+                if fn is not uncached:
+                    counts[mode][fn.__name__][0] += cache.misses - m
+                    counts[mode][fn.__name__][1] += cache.hits - h
+            rounds[mode].append(row)
+    model.batch_ids = None
+    med = {mode: [statistics.median(r[i] for r in rounds[mode]) for i in range(len(variants))] for mode in modes}
+    spread = {mode: [round(min(r[0] for r in rounds[mode]), 3), round(max(r[0] for r in rounds[mode]), 3)] for mode in modes}
+    ta, tb, tc = med["default"][:3]
+    ia, ib, ic = med["pass_invariant"][:3]
+
+    x = frames if frames.dim() == 5 else frames.unsqueeze(2)
+    ae.set_pass_invariant(False)
+    bits = bits_check(ae, cache, x, ids, n, bt, dev)
+    pass_frames, bypassed = cache.pass_frames.get("train"), cache.bypassed
+    ae.set_pass_invariant(True)
+    bits_inv = bits_check(ae, cache, x, ids, n, bt, dev)
+    bypassed_inv = cache.bypassed - bypassed
+    ae.set_pass_invariant(False)
+    shape = cache.latent_shape
     big = (max(1, min(a.capacity, 8192) // 16), 16)
     cache.table.normal_()           # the big gather reads every row: give the rows nobody wrote a value
+    names = [fn.__name__ for fn in variants]
     line = {"case": name, "frames": list(frames.shape), "precision": prec, "latent": list(shape), "sample": bool(ae.sample),
             "row_KiB": cache.table.shape[1] * 4 / 1024, "capacity_frames": cache.capacity, "table_MiB": cache.bytes / 2 ** 20,
             "train_step_ms": {"uncached": round(ta, 3), "all_miss": round(tb, 3), "all_hit": round(tc, 3),
                               "uncached_over_all_hit": round(ta / tc, 2)},
-            "miss_overhead_ms": {"all_miss_minus_uncached": round(tb - ta, 3),
-                                 "uncached_spread": [round(min(a_runs), 3), round(max(a_runs), 3)]},
-            "rounds_uncached_miss_hit": [[round(v, 3) for v in r] for r in rounds],
-            "counted": {k: {"misses": v[0], "hits": v[1]} for k, v in counts.items()},
-            "cached_bits_equal_uncached": {"miss": bool(torch.equal(plain, missed)), "hit": bool(torch.equal(plain, hit)),
-                                           "partial_miss_of_k_frames": partial},
-            "pass_frames": cache.pass_frames.get("train"), "bypassed": cache.bypassed,
+            "miss_overhead_ms": {"all_miss_minus_uncached": round(tb - ta, 3), "uncached_spread": spread["default"]},
+            "rounds_uncached_miss_hit": [[round(v, 3) for v in r[:3]] for r in rounds["default"]],
+            "counted": {k: {"misses": v[0], "hits": v[1]} for k, v in counts["default"].items()},
+            "cached_bits_equal_uncached": bits,
+            "pass_frames": pass_frames, "bypassed": bypassed,
+            # the same step with the provider in pass-invariant mode (--invariant-encode), alternated with the above
+            "pass_invariant": {
+                "train_step_ms": {"uncached": round(ia, 3), "all_miss": round(ib, 3), "all_hit": round(ic, 3)},
+                "uncached_minus_default_uncached_ms": round(ia - ta, 3),
+                "uncached_spread": spread["pass_invariant"], "default_uncached_spread": spread["default"],
+                "rounds_uncached_miss_hit": [[round(v, 3) for v in r[:3]] for r in rounds["pass_invariant"]],
+                "counted": {k: {"misses": v[0], "hits": v[1]} for k, v in counts["pass_invariant"].items()},
+                "cached_bits_equal_uncached": bits_inv, "bypassed": bypassed_inv},
+            # a step with k of the batch's frames missing: the default mode encodes whole passes, the other mode k frames
+            "partial_miss_step_ms": {mode: {names[i][len("partial_"):]: round(med[mode][i], 3) for i in range(3, len(variants))}
+                                     for mode in modes},
             "gather_step": gather_alone(cache.table, shape, ae.sample, bt, 200, dev),
             "gather_table": gather_alone(cache.table, shape, ae.sample, big, 20, dev)}
     ae.cache = None

@@ -24,7 +24,9 @@ class LatentCache:
     `Autoencoder._encode_cached`: the encoder's GEMM routes depend on it, so it is part of what a row is).
     Counters: `misses` frames that were encoded, `hits` frames that were asked for and not encoded (read from the table,
     or a repeat inside one batch of a frame encoded in that step: `hits` is not the number of table reads), `bypassed`
-    frames of batches that went around the cache, `frames_cached` slots in use, `bytes` of the table."""
+    frames of batches that went around the cache, `frames_cached` slots in use, `bytes` of the table.
+    With a pass-invariant provider (`Autoencoder.pass_invariant`) a row does not depend on its pass: `pass_frames` and
+    `serves` are not used and `bypassed` stays 0."""
 
     def __init__(self, capacity):
         self.capacity = int(capacity)
@@ -107,7 +109,10 @@ class Autoencoder(tnn.Module):
     dict, or a Lightning checkpoint that holds it under the `autoencoder.` / `model.` prefix, other modules' keys next to
     it being ignored), else a seeded initialisation
     (`cfg.seed`, default 0).  encode returns the posterior's mode; frames go through in chunks of `cfg.chunk_frames`
-    (default 8; 0 = all B*T frames in one pass).  With `cfg.sample: true` (ae_s2) encode returns a sample instead,
+    (default 8; 0 = all B*T frames in one pass).  `cfg.pass_invariant: true` (the drivers' --invariant-encode; this kind
+    only) puts the model into `AutoencoderKL.pass_invariant()` mode: a frame's latent is then the same bits in every pass,
+    and a cache encodes exactly the frames it misses (`_encode_cached`).
+    With `cfg.sample: true` (ae_s2) encode returns a sample instead,
     z = mean + std * noise, the noise drawn as the reference's loop over T draws it (`draw_noise`).
     kind "ae_gan.convautoencoder": the residual `ConvAutoencoderBIG` of ae_gan in evaluation mode (`cfg.latent_dim`, default
     2048; `cfg.checkpoint` / `cfg.seed` as for autoencoder_kl): encode (B, T, 1, 128, 128) -> (B, T, latent_dim, 1, 1), decode
@@ -125,11 +130,17 @@ class Autoencoder(tnn.Module):
         self.chunk_frames = 0
         self.sample = False
         self.cache = None
+        self.pass_invariant = False
+        if (cfg or {}).get("pass_invariant") is not None and kind != "autoencoder_kl":
+            raise WfaeError(f"autoencoder.pass_invariant belongs to kind 'autoencoder_kl', not to {kind!r}: only the frozen "
+                            "AutoencoderKL has a pass-invariant form")
         if kind == "autoencoder_kl":
             self.autoencoder = self._build_autoencoder_kl(cfg or {})
             chunk = (cfg or {}).get("chunk_frames")
             self.chunk_frames = 8 if chunk is None else int(chunk)      # 0: all B*T frames in one pass
             self.sample = bool((cfg or {}).get("sample") or False)
+            if (cfg or {}).get("pass_invariant"):
+                self.set_pass_invariant()
             if self.chunk_frames < 0:
                 raise ValueError(f"autoencoder.chunk_frames={self.chunk_frames}")
         elif kind == "ae_gan.convautoencoder":
@@ -192,6 +203,19 @@ class Autoencoder(tnn.Module):
             torch.randn((b, *latent_shape), generator=generator, device=device, dtype=torch.float32, out=noise[i])
         return noise
 
+    def set_pass_invariant(self, flag=True):
+        """put the frozen AutoencoderKL into (or take it out of) `AutoencoderKL.pass_invariant()` mode: a frame's latent
+        no longer depends on the frames that share its encoder pass.  A cache filled in the other mode is emptied"""
+        if self.kind != "autoencoder_kl":
+            raise WfaeError(f"Autoencoder.set_pass_invariant: kind {self.kind!r} has no pass-invariant form, only "
+                            "autoencoder_kl has (its attention projections then run on the row-invariant linear kernel)")
+        self.autoencoder.pass_invariant(flag)
+        if self.cache is not None and bool(flag) != self.pass_invariant:
+            self.cache.clear()
+            self.cache.pass_frames.clear()
+        self.pass_invariant = bool(flag)
+        return self
+
     def enable_cache(self, capacity_frames):
         """keep the latents of up to `capacity_frames` frames on the device (`LatentCache`); `encode(x, ids=...)` then
         encodes a frame once.  -> the cache"""
@@ -214,16 +238,23 @@ class Autoencoder(tnn.Module):
         missing frames are encoded in passes of exactly the size the uncached encode uses, filled up with repeats of the
         last missing frame whose results are dropped; one missing frame costs one whole pass.  A batch whose uncached
         passes are not all of that size (`LatentCache.serves`) is encoded as without the cache and neither read from
-        nor written to the table"""
+        nor written to the table.
+        A pass-invariant provider has no such dependence (the projections run on linear_fwd_rowinv), so every batch is
+        served, short ones and tail chunks included, and exactly the unique missing frames are encoded: in passes of at
+        most `chunk_frames` frames, or in one pass when that is 0, with no fill-up repeats; a frame past the capacity
+        costs itself"""
         b, t, c, h, w = x.shape
         split, fid = ids
         fid = np.asarray(fid).reshape(-1)
         if fid.size != b * t:
             raise WfaeError(f"Autoencoder.encode: {fid.size} frame ids for a batch of {b} x {t} frames")
         cache = self.cache
-        size = cache.serves(split, b * t, self.chunk_frames)
-        if not size:
-            return None
+        if self.pass_invariant:
+            size = 0
+        else:
+            size = cache.serves(split, b * t, self.chunk_frames)
+            if not size:
+                return None
         keys = [(split, int(i)) for i in fid]
         missing, slots, index = cache.plan(keys)
         fresh = None
@@ -233,7 +264,10 @@ class Autoencoder(tnn.Module):
                 for f, k in enumerate(keys):
                     first.setdefault(k, f)
                 rows = [first[k] for k in missing]
-                rows += [rows[-1]] * (-len(rows) % size)          # whole passes of `size` frames
+                if self.pass_invariant:
+                    size = self.chunk_frames if self.chunk_frames > 0 else len(rows)    # the last pass may be short
+                else:
+                    rows += [rows[-1]] * (-len(rows) % size)          # whole passes of `size` frames
                 frames = x.reshape(b * t, c, h, w)
                 if rows != list(range(b * t)):
                     frames = frames[torch.as_tensor(rows, device=x.device)]
@@ -262,7 +296,8 @@ class Autoencoder(tnn.Module):
         """x (B, T, 1, H, W) -> (B, T, C, h, w).  `generator` / `noise` (T, B, C, h, w) belong to `sample: true`: `noise`
         replaces the draw.  `ids` = (split, the B*T int64 frame ids in (b, t) order) names the frames for the cache of
         `enable_cache`: the result is the same bits, frames met before are not encoded again (a batch whose encoder
-        passes are not of the cached size goes around the cache).  Without a cache `ids` is not read, and without `ids`
+        passes are not of the cached size goes around the cache, unless the provider is pass-invariant).  Without a cache
+        `ids` is not read, and without `ids`
         the cache is not used"""
         b, t, c, h, w = x.shape
         frames = x.reshape(b * t, c, h, w)

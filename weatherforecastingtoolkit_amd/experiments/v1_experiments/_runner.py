@@ -194,7 +194,8 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
     `__main__` calls trainer.test after trainer.fit; `--no-test` leaves it out).  `--latent-cache FRAMES` keeps the frozen
     AutoencoderKL's latents on the device (`enable_latent_cache`): the training, validation and test-after-fit steps get
     their batch's frame ids in `model.batch_ids`, and one `latent_cache` line is printed in front of `done`; with
-    `--mode test` the flag is refused"""
+    `--mode test` the flag is refused.  `--invariant-encode` puts that provider into pass-invariant mode
+    (`enable_invariant_encode`), with or without the cache"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default=os.path.join(here, "config.yaml"))
     ap.add_argument("--max-steps", type=int, default=-1)
@@ -221,7 +222,13 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
                          "encoded once per run and not once per epoch (each rank caches its own shard; a resumed run "
                          "refills it).  The run's numbers are bit for bit those without the flag: missing frames are "
                          "encoded in passes of the size the uncached encode uses, and a batch of another pass size (a "
-                         "short last batch) goes around the cache.  Fit only.  0 = off")
+                         "short last batch) goes around the cache; with --invariant-encode exactly the missing frames "
+                         "are encoded and no batch goes around.  Fit only.  0 = off")
+    ap.add_argument("--invariant-encode", action="store_true",
+                    help="frozen AutoencoderKL providers: make a frame's latent the same bits whatever shares its encoder "
+                         "pass (the attention projections run on the row-invariant linear kernel).  The latents differ "
+                         "from the default mode's in the last bits.  With --latent-cache the cache then encodes exactly "
+                         "the frames it misses, and serves short batches and tail chunks too")
     ap.add_argument("--stop-after", type=int, default=-1,
                     help="stop (and checkpoint) after this many optimiser steps without changing the schedule: an "
                          "interrupted run that --resume continues")
@@ -253,6 +260,8 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
     model = build(cfg, size).to(dev).train()
     if getattr(model, "autoencoder", None) is not None:
         model.autoencoder.eval()
+    if args.invariant_encode:
+        enable_invariant_encode(model)
     cache = enable_latent_cache(model, loader, args.latent_cache) if args.latent_cache else None
     # the figures' sink: rank 0's, and only with --plots; a model's steps draw nothing while `panels` is None
     model.panels = helpers.make_sink(args.plots, rank, cfg.trainer, total, len(loader) if mode == "test" else len(val),
@@ -344,6 +353,18 @@ def enable_latent_cache(model, loader, frames):
         raise WfaeError(f"--latent-cache: the training loader augments (dataset.aug_mode {aug!r}), so a frame differs from "
                         "epoch to epoch and its latent cannot be kept; the flag needs aug_mode \"0\"")
     return cache
+
+
+def enable_invariant_encode(model):
+    """`--invariant-encode`: the model's frozen provider in pass-invariant mode, or the reason the run cannot have it"""
+    ae = getattr(model, "autoencoder", None)
+    if not isinstance(ae, Autoencoder):
+        raise WfaeError(f"--invariant-encode: {type(model).__module__}.Model has no frozen latent provider "
+                        "(_latents.Autoencoder) to put into pass-invariant mode: it trains on frames or on its own encoder")
+    if ae.kind != "autoencoder_kl":
+        raise WfaeError(f"--invariant-encode: the provider is of kind {ae.kind!r}; only the frozen AutoencoderKL "
+                        "(autoencoder.kind autoencoder_kl) has a pass-invariant form")
+    return ae.set_pass_invariant()
 
 
 class batch_ids:

@@ -1390,23 +1390,48 @@ def aekl_conv3x3(x, packed, cout, bias=None, gn=None, res=None, kind=0, out_mul=
                               None if res is None else _c(res.detach()), int(kind), mode, float(out_mul))
 
 
-def aekl_attention(x, gn, wq, bq, wk, bk, wv, bv, wo, bo, rescale=1.0):
+def aekl_attention(x, gn, wq, bq, wk, bk, wv, bv, wo, bo, rescale=1.0, row_invariant=False):
     """single-head AttentionBlock on x (N, C, H, W) with the folded GroupNorm affine gn = (scale, shift):
-    (proj(softmax(q k^T / sqrt C) v) + x) / rescale.  The four products run on linear_fwd / split_gemm."""
+    (proj(softmax(q k^T / sqrt C) v) + x) / rescale.  The four products run on linear_fwd / split_gemm; with
+    `row_invariant` on linear_fwd_rowinv, whose result for a token does not depend on how many samples share the call."""
     _aekl_no_grad("aekl_attention", x)
     x = _c(x.detach())
     n, c, h, w = x.shape
     s = h * w
     planes = 1 if ops.get_float32_matmul_precision() == "medium" else 3
+    linear = ops.linear_fwd_rowinv if row_invariant else ops.linear_fwd
     tok = ops.aekl_to_tokens(x, gn).view(n * s, c)
-    q = ops.linear_fwd(tok, wq.detach(), bq.detach()).view(n, s, c)
-    k = ops.linear_fwd(tok, wk.detach(), bk.detach()).view(n, s, c)
-    v = ops.linear_fwd(tok, wv.detach(), bv.detach()).view(n, s, c)
+    q = linear(tok, wq.detach(), bq.detach()).view(n, s, c)
+    k = linear(tok, wk.detach(), bk.detach()).view(n, s, c)
+    v = linear(tok, wv.detach(), bv.detach()).view(n, s, c)
     scores = ops.split_gemm(ops.split_bf16x3(q, planes), ops.split_bf16x3(k, planes), b_kind=1)   # (n, s, s)
     probs = ops.aekl_softmax(scores, 1.0 / float(c) ** 0.5)
     ctxv = ops.split_gemm(ops.split_bf16x3(probs, planes), ops.split_bf16x3(v, planes), b_kind=0)   # (n, s, c)
-    out = ops.linear_fwd(ctxv.view(n * s, c), wo.detach(), bo.detach()).view(n, s, c)
+    out = linear(ctxv.view(n * s, c), wo.detach(), bo.detach()).view(n, s, c)
     return ops.aekl_from_tokens(out, x.shape, x, 1.0 / float(rescale))
+
+
+def aekl_conv1x1_rowinv(x, w, bias=None):
+    """1x1 convolution of the frozen provider, x (N, Cin, H, W), w (Cout, Cin[, 1, 1]), whose result for a sample does not
+    depend on the batch size.  ops.conv1x1_fwd with a bias runs on gemm.hip, which from Cin >= 128 and Cout >= 64 on chooses
+    between the three-plane split and the fp32 matrix instruction by the column count N H W (`launch_gemm_v`, `pick_bm`).
+    So: channel counts and H W that are multiples of 32 go through tokens — to_tokens, linear_fwd_rowinv, from_tokens, the
+    two layout kernels being copies; below Cin = 128 the default kernel has one instruction and one k-order for every batch
+    size and is kept; anything else is refused."""
+    _aekl_no_grad("aekl_conv1x1_rowinv", x)
+    x = _c(x.detach())
+    n, c, h, wd = x.shape
+    cout = w.shape[0]
+    w2 = w.detach().reshape(cout, c)
+    b = None if bias is None else bias.detach()
+    if c % 32 == 0 and cout % 32 == 0 and (h * wd) % 32 == 0 and max(c, cout) <= 4096:
+        tok = ops.aekl_to_tokens(x).view(n * h * wd, c)
+        out = ops.linear_fwd_rowinv(tok, w2, b).view(n, h * wd, cout)
+        return ops.aekl_from_tokens(out, (n, cout, h, wd))
+    if c >= 128:
+        raise ops._lib.WfaeError(f"aekl_conv1x1_rowinv: Cin={c}, Cout={cout}, H*W={h * wd}: from Cin = 128 on the pass-invariant "
+                                 "form needs channel counts and H*W that are multiples of 32 (channels up to 4096)")
+    return ops.conv1x1_fwd(x, w2, b)
 
 
 def aekl_posterior(moments, noise=None):

@@ -710,6 +710,22 @@ def linear_fwd(x, w, bias=None):
     return y
 
 
+def linear_fwd_rowinv(x, w, bias=None):
+    """x (B, In) @ w (Out, In)^T + bias like linear_fwd, with the bits of a result row a function of that row of x, of w,
+    bias and the matmul precision alone: not of B, of the row's place, of the other rows, nor of the pointers' alignment
+    (include/wfae.h "row-invariant nn.Linear forward"; csrc/linear_rowinv.hip).  In and Out: multiples of 32 up to 4096"""
+    _chk(x, w, bias)
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1] or (bias is not None and tuple(bias.shape) != (w.shape[0],)):
+        raise _lib.WfaeError(f"linear_fwd_rowinv: expected x (B, In), w (Out, In) and bias (Out), got {tuple(x.shape)}, "
+                             f"{tuple(w.shape)} and {None if bias is None else tuple(bias.shape)}")
+    b, inf = x.shape
+    out = w.shape[0]
+    y = torch.empty((b, out), dtype=x.dtype, device=x.device)
+    _call("wfae_linear_fwd_rowinv", 2 * b * inf * out, 4 * (inf * out + b * (inf + out)), _p(x), _p(w), _p(bias), _p(y), b, inf,
+          out, _stream(), peak=_default_peak())
+    return y
+
+
 def linear_bwd_data(dy, w):
     _chk(dy, w)
     b, out = dy.shape

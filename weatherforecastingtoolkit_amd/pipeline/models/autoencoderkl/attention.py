@@ -22,6 +22,7 @@ class AttentionBlock(tnn.Module):
         self.value = tnn.Linear(channels, channels)
         self.rescale_output_factor = rescale_output_factor
         self.proj_attn = tnn.Linear(channels, channels, bias=True)
+        self.row_invariant = False      # `AutoencoderKL.pass_invariant()`: the projections on linear_fwd_rowinv (frozen only)
 
     def forward(self, x):
         if x.dim() != 4 or x.shape[1] != self.channels:
@@ -32,6 +33,8 @@ class AttentionBlock(tnn.Module):
                             f"C={self.channels})")
         q, k, v, o = self.query, self.key, self.value, self.proj_attn
         if trains(q.weight):
+            if self.row_invariant:
+                raise WfaeError("AttentionBlock: row_invariant belongs to the frozen provider, the training path has no such form")
             return Fn.aekl_attention_train(x, self.group_norm, q, k, v, o, self.rescale_output_factor)
         return Fn.aekl_attention(x, group_norm_affine(self.group_norm, x), q.weight, q.bias, k.weight, k.bias, v.weight,
-                                 v.bias, o.weight, o.bias, self.rescale_output_factor)
+                                 v.bias, o.weight, o.bias, self.rescale_output_factor, row_invariant=self.row_invariant)

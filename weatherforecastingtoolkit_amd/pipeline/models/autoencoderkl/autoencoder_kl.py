@@ -36,6 +36,7 @@ class AutoencoderKL(tnn.Module):
         self.quant_conv = tnn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
         self.post_quant_conv = tnn.Conv2d(latent_channels, latent_channels, 1)
         self.use_slicing = False
+        self.invariant = False
         self.freeze()
 
     def freeze(self):
@@ -49,9 +50,30 @@ class AutoencoderKL(tnn.Module):
     def unfreeze(self):
         """opt into training: parameters require gradients, `train(mode)` behaves as for any module, and `encode` /
         `decode` / `forward` build a graph when autograd is recording"""
+        if self.invariant:
+            raise WfaeError("AutoencoderKL.unfreeze: the model is in pass-invariant mode, which belongs to the frozen provider "
+                            "(the training path has no row-invariant kernels): call pass_invariant(False) first")
         self.trainable = True
         for p in self.parameters():
             p.requires_grad_(True)
+        return self
+
+    def pass_invariant(self, flag=True):
+        """frozen provider only: make the result for a sample the same bits whatever else shares its `encode` / `decode`
+        call.  Two things depend on the pass size: the summation order of the four projections of every `AttentionBlock`
+        (their GEMM rows are samples x tokens), and the instruction of the 1x1 convolutions with 128 or more input channels
+        (the ResNet shortcuts, `quant_conv`, `post_quant_conv`: gemm.hip picks the split or the fp32 form by the column
+        count).  With the flag both run on ops.linear_fwd_rowinv (functional.aekl_attention(row_invariant=True),
+        functional.aekl_conv1x1_rowinv).  The values differ from the default mode's in the last bits, and so do not
+        replace it silently.  -> self"""
+        if self.trainable:
+            raise WfaeError("AutoencoderKL.pass_invariant: the model is unfrozen; pass-invariant mode belongs to the frozen "
+                            "provider (freeze() first)")
+        from .attention import AttentionBlock
+        self.invariant = bool(flag)
+        for m in self.modules():
+            if isinstance(m, AttentionBlock) or (isinstance(m, tnn.Conv2d) and tuple(m.kernel_size) == (1, 1)):
+                m.row_invariant = self.invariant
         return self
 
     def train(self, mode=True):

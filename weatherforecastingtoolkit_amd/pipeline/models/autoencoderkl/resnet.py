@@ -68,9 +68,12 @@ def group_norm_affine(norm, x):
 
 
 def conv1x1(conv, x):
-    """nn.Conv2d(cin, cout, 1) on the 1x1 kernels"""
+    """nn.Conv2d(cin, cout, 1) on the 1x1 kernels; with `conv.row_invariant` (`AutoencoderKL.pass_invariant()`, frozen only) on
+    the form whose result for a sample does not depend on the batch"""
     if trains(conv.weight):
         return Fn.conv1x1(x, conv.weight, conv.bias)
+    if getattr(conv, "row_invariant", False):
+        return Fn.aekl_conv1x1_rowinv(x, conv.weight, conv.bias)
     return ops.conv1x1_fwd(x, conv.weight.detach().view(conv.out_channels, conv.in_channels), conv.bias.detach())
 
 
