@@ -836,6 +836,9 @@ int wfae_skill_scores(const float* pred, const float* target, int64_t* out, int 
 int wfae_ensemble_mean(const float* pred, float* out, int64_t outer, int N, int64_t inner, int clamp01,
                        wfae_stream_t stream);
 
+/* ---- forecast verification per lead time (csrc/verify.hip): wfae_verify_leads, declared in a header of its own. */
+#include "wfae_verify.h"
+
 /* ---- latent transformer of the `_tf` variant (pipeline/models/ae_64x8x8_tf.py:77-80,107-109):
  * nn.TransformerEncoderLayer(d_model=64, nhead=8, dim_feedforward=2048, dropout=0.1), post-norm, ReLU,
  * batch_first=False.  The Linear layers use wfae_linear_*.

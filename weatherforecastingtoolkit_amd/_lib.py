@@ -14,6 +14,8 @@ import re
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 HEADER = os.path.join(_ROOT, "include", "wfae.h")
+# headers that wfae.h includes; `parse_header()` reads one file, `load()` binds the declarations of all of them
+INCLUDED_HEADERS = (os.path.join(_ROOT, "include", "wfae_verify.h"),)
 LIB_PATH = os.path.join(_PKG, "libwfae.so")
 
 _CT = {
@@ -85,11 +87,13 @@ def load(path: str = LIB_PATH):
             "(weatherforecastingtoolkit_amd/csrc/build.sh). There is no CPU fallback.")
     lib = ctypes.CDLL(path)
     decls = parse_header()
+    for extra in INCLUDED_HEADERS:
+        decls.update(parse_header(extra))
     for name, (restype, argtypes, _) in decls.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
-            raise WfaeError(f"libwfae.so does not export {name} declared in include/wfae.h") from e
+            raise WfaeError(f"libwfae.so does not export {name} declared in include/wfae.h or a header it includes") from e
         fn.restype = restype
         fn.argtypes = argtypes
     _lib, _decls = lib, decls

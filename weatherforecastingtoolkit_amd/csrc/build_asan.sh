@@ -9,8 +9,8 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -fno-gpu-sanitize -O1 -g -std=c++17 -fPIC -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Wno-unused-result"
 mkdir -p build_asan
 pids=()
-for f in api gemm dconv norm_act loss ssim skill transformer wino forecast dlinear prediff convae aekl aekl_bwd lpips vit c1conv splitgemm c1b c1w g3b c1r c1rb c1n c1wd c1ws augment vil_pool c3s2 convattn resae resae_bwd panels latent_cache linear_rowinv; do
-  if [ ! -f build_asan/$f.o ] || [ $f.hip -nt build_asan/$f.o ] || [ common.h -nt build_asan/$f.o ] || [ resae_common.h -nt build_asan/$f.o ] || [ ../../include/wfae.h -nt build_asan/$f.o ]; then
+for f in api gemm dconv norm_act loss ssim skill transformer wino forecast dlinear prediff convae aekl aekl_bwd lpips vit c1conv splitgemm c1b c1w g3b c1r c1rb c1n c1wd c1ws augment vil_pool c3s2 convattn resae resae_bwd panels latent_cache linear_rowinv verify; do
+  if [ ! -f build_asan/$f.o ] || [ $f.hip -nt build_asan/$f.o ] || [ common.h -nt build_asan/$f.o ] || [ resae_common.h -nt build_asan/$f.o ] || [ ../../include/wfae.h -nt build_asan/$f.o ] || [ ../../include/wfae_verify.h -nt build_asan/$f.o ]; then
     $HIPCC $FLAGS -c $f.hip -o build_asan/$f.o &
     pids+=($!)
   fi

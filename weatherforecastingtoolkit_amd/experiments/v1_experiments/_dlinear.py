@@ -265,12 +265,14 @@ class Model(Step, tnn.Module):
     def validation_step(self, batch, batch_idx=0, split="val"):
         """-> (loss, logs): logs holds `{split}_loss` and, when the provider decodes, the `{split}_` calc_metrics keys
         of the decoded forecast against the decoded target (reference :180-203)"""
-        _, v = self.frames_latents(batch)
-        return self.validate_latents(v, batch_idx, split)
+        frames, v = self.frames_latents(batch)
+        return self.validate_latents(v, batch_idx, split, frames=frames)
 
     @torch.no_grad()
-    def validate_latents(self, v, batch_idx=0, split="val"):
-        """validation_step on latents (B, T, C, h, w)"""
+    def validate_latents(self, v, batch_idx=0, split="val", frames=None):
+        """validation_step on latents (B, T, C, h, w).  `frames` (B, T, 1, H, W): the observed frames behind `v`; with
+        `verification` set they score the decoded forecast, persistence (the last input frame, lead stride 0) and the
+        decoded target (the autoencoder's floor) per lead in one launch pair, from views of the batch"""
         loss, pred, rows = self.latent_loss(v)
         logs = {f"{split}_loss": loss}
         ae = self.autoencoder
@@ -282,6 +284,10 @@ class Model(Step, tnn.Module):
             tgt = ops.dlinear_forecast(ops.dlinear_target(rows, L, P, f), rows, L, f).view(shape)
             decoded_pred, decoded_tgt = ae.decode(fc), ae.decode(tgt)
             logs.update(helpers.log_metrics(decoded_pred, decoded_tgt, split))
+            if self.verification is not None and frames is not None:
+                n = self.input_frames
+                self.verification.add({"forecast": decoded_pred, "persistence": frames[:, n - 1],
+                                       "reconstruction": decoded_tgt}, frames[:, n:])
             if self.panels is not None:
                 epochs, key, prefix, suffix = self.plot_style
                 e, tv = self.panels.epoch, self.panels.total("val")     # every script times both splits by total_val_steps

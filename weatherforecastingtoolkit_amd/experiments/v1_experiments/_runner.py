@@ -35,6 +35,7 @@ class Step:
 
     trained = "predictor"        # the attribute that holds the trained sub-module
     panels = None                # helpers.PanelSink with `--plots DIR` on rank 0: the steps that plot draw into it
+    verification = None          # metrics.LeadVerification with `--verify`: the validation / test steps add to it
     exact_complements = False    # see optim.FusedAdamW
     batch_ids = None             # with `--latent-cache`: (split, frame ids) of the loader batch the driver hands to a step
 
@@ -195,7 +196,9 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
     AutoencoderKL's latents on the device (`enable_latent_cache`): the training, validation and test-after-fit steps get
     their batch's frame ids in `model.batch_ids`, and one `latent_cache` line is printed in front of `done`; with
     `--mode test` the flag is refused.  `--invariant-encode` puts that provider into pass-invariant mode
-    (`enable_invariant_encode`), with or without the cache"""
+    (`enable_invariant_encode`), with or without the cache.  `--verify` (`enable_verification`) gives the DLinear
+    forecasters a `metrics.LeadVerification`: every validation / test pass, `--mode test` included, starts with empty
+    tables and ends with one `verification` line after its own (`report_verification`); no other line changes"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default=os.path.join(here, "config.yaml"))
     ap.add_argument("--max-steps", type=int, default=-1)
@@ -229,6 +232,11 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
                          "pass (the attention projections run on the row-invariant linear kernel).  The latents differ "
                          "from the default mode's in the last bits.  With --latent-cache the cache then encodes exactly "
                          "the frames it misses, and serves short batches and tail chunks too")
+    ap.add_argument("--verify", action="store_true",
+                    help="DLinear forecasters: score the decoded forecast, persistence (the last input frame) and the "
+                         "decoded target against the observed frames per lead time in every validation / test pass, and "
+                         "print one `verification` line per pass: MSE, MAE, CSI, HSS per lead and field, the MSE skill "
+                         "against persistence and the leads at which the forecast beats it")
     ap.add_argument("--stop-after", type=int, default=-1,
                     help="stop (and checkpoint) after this many optimiser steps without changing the schedule: an "
                          "interrupted run that --resume continues")
@@ -263,12 +271,16 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
     if args.invariant_encode:
         enable_invariant_encode(model)
     cache = enable_latent_cache(model, loader, args.latent_cache) if args.latent_cache else None
+    if args.verify:
+        enable_verification(model)
     # the figures' sink: rank 0's, and only with --plots; a model's steps draw nothing while `panels` is None
     model.panels = helpers.make_sink(args.plots, rank, cfg.trainer, total, len(loader) if mode == "test" else len(val),
                                      len(loader) if mode == "test" else len(test))
     step = 0
     if mode == "test":
         model.eval()
+        if getattr(model, "verification", None) is not None:
+            model.verification.reset()
         for i in range(min(total, len(loader))):
             if model.panels is not None:
                 model.panels.global_step = step
@@ -276,6 +288,7 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
             step += 1
             if rank == 0:
                 print(json.dumps({"step": step, **{k: float(v) for k, v in logs.items()}}), flush=True)
+        report_verification(model, "test", step, rank, world)
         if rank == 0:
             print("done")
         return 0
@@ -322,13 +335,16 @@ def run(here, argv, build, *, default_mode=None, layout=lambda cfg: "NTHW", rate
             # the validation loop at the end of every training epoch; the one after the last step follows the checkpoint
             report(evaluate(model, val, "val", cfg.trainer.limit_val_batches, world, step, nb), rank, step=step,
                    epoch=(step - 1) // nb)
+            report_verification(model, "val", step, rank, world)
     if rank == 0:
         save_checkpoint(last, model, state, step, step // nb)
     if validating and step >= total:
         report(evaluate(model, val, "val", cfg.trainer.limit_val_batches, world, step, nb), rank, step=step,
                epoch=(step - 1) // nb)
+        report_verification(model, "val", step, rank, world)
     if args.test:
         report(evaluate(model, test, "test", cfg.trainer.limit_test_batches, world, step, nb), rank)
+        report_verification(model, "test", step, rank, world)
     if rank == 0:
         if cache is not None:
             print(json.dumps({"latent_cache": cache.stats()}), flush=True)
@@ -353,6 +369,35 @@ def enable_latent_cache(model, loader, frames):
         raise WfaeError(f"--latent-cache: the training loader augments (dataset.aug_mode {aug!r}), so a frame differs from "
                         "epoch to epoch and its latent cannot be kept; the flag needs aug_mode \"0\"")
     return cache
+
+
+def enable_verification(model):
+    """`--verify`: a LeadVerification in `model.verification`, or the reason the run cannot have one"""
+    from ...pipeline import metrics
+    what = f"{type(model).__module__}.Model"
+    if not isinstance(model, Step) or not hasattr(model, "validate_latents"):
+        raise WfaeError(f"--verify: {what} has no validation step that decodes its forecast (validate_latents); the flag "
+                        "belongs to the DLinear forecasters (pretrained_ae_dlinear_*, ae_s2)")
+    ae = getattr(model, "autoencoder", None)
+    if ae is None:
+        raise WfaeError(f"--verify: {what} has no latent provider: without frames and a decoder there is no forecast in "
+                        "frame space to hold against persistence")
+    if not getattr(ae, "can_decode", lambda: False)():
+        raise WfaeError(f"--verify: the latent provider of kind {getattr(ae, 'kind', type(ae).__name__)!r} cannot decode, "
+                        "so the forecast never reaches frame space")
+    model.verification = metrics.LeadVerification(("forecast", "persistence", "reconstruction"), model.pred_frames)
+    return model.verification
+
+
+def report_verification(model, split, step, rank, world):
+    """the `verification` line of a pass that ended (rank 0); every rank takes part in the sum over ranks"""
+    v = getattr(model, "verification", None)
+    if v is None:
+        return
+    v.merge(world)
+    res = v.result()
+    if rank == 0:
+        print(json.dumps({"verification": res if "skipped" in res else dict(split=split, step=step, **res)}), flush=True)
 
 
 def enable_invariant_encode(model):
@@ -491,6 +536,8 @@ def evaluate(model, loader, split, limit, world, step=None, nb_train=1):
     in evaluation mode; the generators and the dropout counter are left where they were, so a pass does not move the run.
     `step`, `nb_train`: the run's optimiser step and batches per epoch, for the sink of `--plots` (index lines, labels)"""
     name = "test_step" if split == "test" else "validation_step"
+    if getattr(model, "verification", None) is not None:
+        model.verification.reset()                      # the tables of `--verify` hold one pass
     if not hasattr(model, name):
         return {"skipped": f"{type(model).__module__}.Model has no {name}"}
     refused = getattr(model, "validation_refused", lambda: None)()

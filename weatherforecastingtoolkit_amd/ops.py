@@ -2330,6 +2330,86 @@ def ensemble_mean(pred, clamp01=False):
     return out
 
 
+# ------------------------------------------------------- verification per lead time (csrc/verify.hip)
+def _frame_strides(name, t, lead_dims, b, p, s):
+    """(sample stride, lead stride) in elements of the view `t`, whose first `lead_dims` axes are (B,) or (B, P or 1) and
+    whose other axes are one frame of `s` contiguous pixels"""
+    want = 1
+    for size, stride in zip(reversed(t.shape[lead_dims:]), reversed(t.stride()[lead_dims:])):
+        if size > 1 and stride != want:
+            raise _lib.WfaeError(f"verify_leads: {name}: a frame must be contiguous, got shape {tuple(t.shape)} with "
+                                 f"strides {t.stride()}")
+        want *= size
+    bs = t.stride(0) if b > 1 else 0
+    ls = t.stride(1) if lead_dims == 2 and t.shape[1] > 1 else 0
+    return bs, ls
+
+
+def verify_leads(fields, target, thresholds, clamp01=True, out=None):
+    """Scores per lead time of up to 4 fields against one target in one launch pair, from views (nothing is copied).
+
+    target (B, P, ...): P leads of frames with S = prod(...) contiguous pixels each, e.g. `frames[:, L:]` of a loader
+    batch.  Every field has the same B and S per frame and is (B, P, ...), or (B, 1, ...) / (B, ...) for one frame held
+    against every lead (lead stride 0: persistence, `frames[:, L - 1]`); the frame axes may be spelled differently
+    ((H, W) against (1, H, W)).  thresholds: up to 8 floats, events are `value >= threshold` in fp32; clamp01 clamps both
+    sides to [0, 1] first.  -> (counts int64 (P, F, 3 * len(thresholds) + 1): [tp, fn, fp] per threshold, then the cells of
+    the lead; sums float64 (P, F, 2): sum of e^2 and of |e|, e = field - target in fp64).  out=(counts, sums): the call
+    adds to these tables and returns them.  No host synchronisation; the same inputs give the same bits."""
+    fields = list(fields)
+    if not 1 <= len(fields) <= 4:
+        raise _lib.WfaeError(f"verify_leads: 1 to 4 fields, got {len(fields)}")
+    if len(thresholds) > 8:
+        raise _lib.WfaeError(f"verify_leads: at most 8 thresholds, got {len(thresholds)}")
+    for name, t in [("target", target)] + [(f"field {i}", f) for i, f in enumerate(fields)]:
+        if not t.is_cuda:
+            raise _lib.WfaeError("wfae kernels need device tensors (the HIP path has no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise _lib.WfaeError(f"verify_leads: {name} must be fp32, got {t.dtype}")
+        if t.device != target.device:
+            raise _lib.WfaeError(f"verify_leads: {name} is on {t.device}, the target on {target.device}")
+    if target.dim() < 3:
+        raise _lib.WfaeError(f"verify_leads: target must be (B, P, ...), got {tuple(target.shape)}")
+    b, p = target.shape[:2]
+    s = math.prod(target.shape[2:])
+    if b < 1 or p < 1 or s < 1:
+        raise _lib.WfaeError(f"verify_leads: empty target {tuple(target.shape)}")
+    tb, tl = _frame_strides("target", target, 2, b, p, s)
+    ptrs, bstr, lstr, moved = [], [], [], target.numel()
+    for i, f in enumerate(fields):
+        shape = tuple(f.shape)
+        if f.dim() >= 3 and shape[0] == b and shape[1] in (p, 1) and math.prod(shape[2:]) == s:
+            lead_dims = 2
+        elif f.dim() >= 2 and shape[0] == b and math.prod(shape[1:]) == s:
+            lead_dims = 1
+        else:
+            raise _lib.WfaeError(f"verify_leads: field {i} {shape} does not match the target {tuple(target.shape)}: "
+                                 f"expected ({b}, {p}, ...), ({b}, 1, ...) or ({b}, ...) with {s} pixels per frame")
+        bs, ls = _frame_strides(f"field {i}", f, lead_dims, b, p, s)
+        ptrs.append(f.data_ptr())
+        bstr.append(bs)
+        lstr.append(ls)
+        moved += b * s * (p if ls else 1)
+    nf, nt = len(fields), len(thresholds)
+    if out is None:
+        counts = torch.empty((p, nf, 3 * nt + 1), dtype=torch.int64, device=target.device)
+        sums = torch.empty((p, nf, 2), dtype=torch.float64, device=target.device)
+    else:
+        counts, sums = out
+        for t, dt, shape in ((counts, torch.int64, (p, nf, 3 * nt + 1)), (sums, torch.float64, (p, nf, 2))):
+            if t.dtype != dt or tuple(t.shape) != shape or t.device != target.device or not t.is_contiguous():
+                raise _lib.WfaeError(f"verify_leads: out must hold a contiguous {dt} tensor of shape {shape} on "
+                                     f"{target.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    fp = (ctypes.c_void_p * nf)(*ptrs)
+    fb = (ctypes.c_int64 * nf)(*bstr)
+    fl = (ctypes.c_int64 * nf)(*lstr)
+    thr = (ctypes.c_float * max(1, nt))(*[float(x) for x in thresholds])
+    ws = workspace(p * min(256, -(-b * s // 1024)) * nf * (3 * nt + 2) * 8)
+    _call("wfae_verify_leads", 0, 4 * moved, ctypes.addressof(fp), ctypes.addressof(fb), ctypes.addressof(fl),
+          target.data_ptr(), tb, tl, nf, b, p, s, ctypes.addressof(thr), nt, int(clamp01), int(out is not None),
+          counts.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return counts, sums
+
+
 # ------------------------------------------------------- latent transformer
 def layernorm_fwd(x, res, gamma, beta, eps=1e-5):
     _chk(x, res, gamma, beta)

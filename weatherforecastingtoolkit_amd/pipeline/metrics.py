@@ -92,6 +92,97 @@ def assemble_metrics(skill, ssim_value, psnr_value):
     return r
 
 
+class LeadVerification:
+    """Scores per lead time of named fields ("forecast", "persistence", "reconstruction", ...) against the observed
+    frames, kept over a pass in two device tables: `counts` int64 (P, F, 3 n_thr + 1) and `sums` float64 (P, F, 2), the
+    layout of ops.verify_leads.  `add` is one launch pair without a host synchronisation, `merge` one all_reduce per table
+    (two tensors, so that a plain sum is right for the integers and for the doubles), `result` one device-to-host copy.
+    Totals over the leads are formed from the summed tables, never from the per-lead scores."""
+
+    def __init__(self, names, pred_frames, thresholds=THRESHOLDS, device=None):
+        self.names, self.pred_frames = tuple(names), int(pred_frames)
+        self.thresholds = [float(t) for t in thresholds]
+        if not 1 <= len(self.names) <= 4 or len(set(self.names)) != len(self.names):
+            raise ValueError(f"LeadVerification: 1 to 4 distinct field names, got {self.names}")
+        self.counts = self.sums = None
+        if device is not None:
+            self._allocate(device)
+
+    def _allocate(self, device):
+        p, f, nt = self.pred_frames, len(self.names), len(self.thresholds)
+        self.counts = torch.zeros((p, f, 3 * nt + 1), dtype=torch.int64, device=device)
+        self.sums = torch.zeros((p, f, 2), dtype=torch.float64, device=device)
+
+    def reset(self):
+        if self.counts is not None:
+            self.counts.zero_()
+            self.sums.zero_()
+
+    def add(self, fields, target):
+        """fields: {name: tensor} for every name (or the tensors in the order of `names`), target (B, P, ...): views as
+        ops.verify_leads takes them; both sides are clamped to [0, 1] like calc_metrics' inputs"""
+        if isinstance(fields, dict):
+            if set(fields) != set(self.names):
+                raise ValueError(f"LeadVerification.add: fields {sorted(fields)} are not {sorted(self.names)}")
+            fields = [fields[n] for n in self.names]
+        if len(fields) != len(self.names) or target.shape[1] != self.pred_frames:
+            raise ValueError(f"LeadVerification.add: {len(fields)} fields against a target {tuple(target.shape)}, expected "
+                             f"{len(self.names)} fields and {self.pred_frames} leads")
+        if self.counts is None:
+            self._allocate(target.device)
+        ops.verify_leads(fields, target, self.thresholds, clamp01=True, out=(self.counts, self.sums))
+
+    def merge(self, world):
+        """sum the tables over the ranks; every rank calls it, also one whose pass held no batch"""
+        if world > 1:
+            import torch.distributed as dist
+            if self.counts is None:
+                self._allocate(torch.device("cuda", torch.cuda.current_device()))
+            dist.all_reduce(self.counts)
+            dist.all_reduce(self.sums)
+
+    def _scores(self, counts, sums):
+        """one field's dict from its count row (3 n_thr + 1) and its two sums"""
+        nt, cells = len(self.thresholds), int(counts[-1])
+        r = {"mse": float(sums[0]) / cells, "mae": float(sums[1]) / cells}
+        pairs = [scores_from_counts(*counts[3 * i:3 * i + 3], cells) for i in range(nt)]
+        for i, (c, h) in enumerate(pairs):
+            r[f"csi_{i}"], r[f"hss_{i}"] = c, h
+        if nt:
+            r["csi_m"] = float(np.mean([c for c, _ in pairs]))
+            r["hss_m"] = float(np.mean([h for _, h in pairs]))
+        return r
+
+    def _entry(self, counts, sums):
+        """{name: scores} of one lead (or of the summed tables) and the MSE skill of every other field against
+        persistence: "skill" for the first field, "skill_<name>" for the others; None where persistence has no error"""
+        e = {n: self._scores(counts[f], sums[f]) for f, n in enumerate(self.names)}
+        if "persistence" in self.names:
+            base = e["persistence"]["mse"]
+            others = [n for n in self.names if n != "persistence"]
+            for n in others:
+                e["skill" if n == others[0] else f"skill_{n}"] = None if base == 0 else 1.0 - e[n]["mse"] / base
+        return e
+
+    def result(self):
+        """-> {"cells_per_lead", "leads": [{"lead": 1 .. P, <name>: {mse, mae, csi_i, hss_i, csi_m, hss_m}, "skill", ...}],
+        "total": the same entry from the tables summed over the leads, "beats_persistence": the leads with skill > 0}, or
+        {"skipped": reason} when the tables hold no cell"""
+        if self.counts is None:
+            return {"skipped": "no frames were verified (the pass held no batch of frames)"}
+        nc = self.counts.numel()
+        host = torch.cat([self.counts.reshape(-1).view(torch.float64), self.sums.reshape(-1)]).cpu().numpy()
+        counts = host[:nc].view(np.int64).reshape(tuple(self.counts.shape))
+        sums = host[nc:].reshape(tuple(self.sums.shape))
+        if int(counts[:, :, -1].min()) == 0:
+            return {"skipped": "no frames were verified (the pass held no batch of frames)"}
+        leads = [dict(lead=p + 1, **self._entry(counts[p], sums[p])) for p in range(self.pred_frames)]
+        out = {"cells_per_lead": int(counts[0, 0, -1]), "leads": leads, "total": self._entry(counts.sum(0), sums.sum(0))}
+        if "persistence" in self.names and len(self.names) > 1:
+            out["beats_persistence"] = [e["lead"] for e in leads if e["skill"] is not None and e["skill"] > 0]
+        return out
+
+
 def crps(pred, target, pool_type="none", scale=1):
     """reference pipeline/metrics.py:18-41 (pred (b, t, c, h, w) or an ensemble (b, n, t, c, h, w))"""
     s = ops.skill_scores(_dense(pred), _dense(target), [], [_pool(pool_type, scale)]).cpu().numpy()
